@@ -9,6 +9,13 @@ reference architecture (seeded reference init + conv_last ~ N(0,1e-3)).  One "st
 forward of one 32-image batch, replayed from a hipGraph.  With N>1 each rank runs its own
 replica on its own shard (inference has no exchange step: weak scaling).
 
+A plain run (`--gpus 1 --steps N --warmup W`) does only what `value` needs: set-up, W warm-up
+and N timed replays, the result line.  `--dump-outputs DIR` also writes the SR batch the last
+timed replay produced (NCHW float32, what a caller of the engine receives) to DIR/sr.npy; the
+inputs and weights are seeded, so two builds can be compared output for output.  Everything
+below beside `value` (the other 16-bit format, psnr_parity, train*, roofline, pcie_inclusive,
+stress, cpu_baseline) runs only with `--full`.
+
 16-bit format: `value` runs in fp16 (--precision), the reference's own mixed-precision
 dtype, at the same MFMA peak as bf16; the metric's "PSNR vs ref" clause (within 0.01 dB,
 north_star) holds in fp16 (measured ~0.002 dB) but not in bf16 (~0.012 dB: bf16's 8-bit
@@ -536,8 +543,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stress", action="store_true")
     ap.add_argument("--precision", choices=["fp16", "bf16"], default="fp16",
-                    help="16-bit format of the headline inference run (the other one is reported beside it)")
+                    help="16-bit format of the headline inference run (with --full the other one is reported "
+                         "beside it)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: roofline of the dominant launch, pcie_inclusive, the other "
+                         "16-bit format, the training legs, the stress config, the CPU baseline and PSNR parity "
+                         "(the --no-* switches trim these; without --full they have nothing to trim)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline run's SR batch of its last timed step to DIR/sr.npy (float32 NCHW)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -566,19 +582,23 @@ def main():
         e.x.copy_(x)
         e.capture()
         tt = timed(e.replay, args.steps, args.warmup, world)
+        last = e.out.detach().cpu().clone()     # what the last timed step computed
+        if not args.full:
+            return e, tt, None, None, None, last
         km, kl, kf = time_dominant_kernel(e)
-        e.replay()
-        torch.cuda.synchronize()
-        return e, tt, km, kl, kf, e.out.detach().cpu().clone()
+        return e, tt, km, kl, kf, last
 
     cpu_model_sd = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_model_sd = build_model("fp32")
     log(f"inference {prec}")
     eng, t, kern_ms, kern_label, kern_flop, out_main = run_inference(prec)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "sr.npy"), out_main.float().numpy())
     value = B * world * args.steps / t
     ms = 1000.0 * t / args.steps
-    achieved = kern_flop / (kern_ms * 1e-3) / 1e12
     out = {
         "metric": "images/sec (64->256 4x SR) at batch 32/GPU",
         "value": round(value, 2),
@@ -597,26 +617,29 @@ def main():
                                "(BASELINE configs[1]; its bf16 run is the 'bf16' leg)",
                    "global_batch": B * world, "per_gpu_batch": B,
                    "parallelism": f"replicas x{world}" if world > 1 else "single"},
-        "roofline": {"bound": "mfma", "kernel": kern_label,
-                     "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "kernel_ms": round(kern_ms, 5),
-                     "flop_per_launch": kern_flop, "traffic": load_traffic(kern_label),
-                     "per_rcab_us_equiv": round(kern_ms * 1e3 * RCAB_CONV_FLOP * 2 / kern_flop, 3)},
     }
-    out["pcie_inclusive"] = time_pcie_inclusive(eng, x, args.steps, args.warmup, world)
-    out["pcie_inclusive"]["pipelined"] = time_pcie_pipelined(eng, x, args.steps, args.warmup, world)
+    if args.full:
+        achieved = kern_flop / (kern_ms * 1e-3) / 1e12
+        out["roofline"] = {"bound": "mfma", "kernel": kern_label,
+                           "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                           "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "kernel_ms": round(kern_ms, 5),
+                           "flop_per_launch": kern_flop, "traffic": load_traffic(kern_label),
+                           "per_rcab_us_equiv": round(kern_ms * 1e3 * RCAB_CONV_FLOP * 2 / kern_flop, 3)}
+        out["pcie_inclusive"] = time_pcie_inclusive(eng, x, args.steps, args.warmup, world)
+        out["pcie_inclusive"]["pipelined"] = time_pcie_pipelined(eng, x, args.steps, args.warmup, world)
     del eng
     torch.cuda.empty_cache()
-    # the same workload in the other 16-bit format (BASELINE configs[1] names bf16)
-    log(f"inference {other}")
-    eng2, t2, k2_ms, _, k2_flop, out_other = run_inference(other)
-    out[other] = {"value": round(B * world * args.steps / t2, 2), "unit": "images/sec",
-                  "ms_per_step": round(1000.0 * t2 / args.steps, 4),
-                  "roofline_frac": round(k2_flop / (k2_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                  "kernel_ms": round(k2_ms, 5)}
-    del eng2
-    torch.cuda.empty_cache()
-    if not args.no_train:
+    if args.full:
+        # the same workload in the other 16-bit format (BASELINE configs[1] names bf16)
+        log(f"inference {other}")
+        eng2, t2, k2_ms, _, k2_flop, out_other = run_inference(other)
+        out[other] = {"value": round(B * world * args.steps / t2, 2), "unit": "images/sec",
+                      "ms_per_step": round(1000.0 * t2 / args.steps, 4),
+                      "roofline_frac": round(k2_flop / (k2_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                      "kernel_ms": round(k2_ms, 5)}
+        del eng2
+        torch.cuda.empty_cache()
+    if args.full and not args.no_train:
         tm = build_model("bf16")
         log("stage-1 L1 training")
         teng = FENEngine(tm, batch=B, lr_hw=(64, 64), dtype=torch.bfloat16, train=True, device="cuda")
@@ -682,7 +705,7 @@ def main():
             if world == 1:
                 log("stage-3 GAN iteration")
                 out["train_gan"] = time_gan_step(args.train_steps)
-    if world == 1 and not args.no_stress:
+    if args.full and world == 1 and not args.no_stress:
         log("stress config (128 ch, x8)")
         out["stress_c128_x8"] = time_stress()
     if cpu_model_sd is not None:

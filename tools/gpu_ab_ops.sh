@@ -45,9 +45,10 @@ PY
    done
   done
 done
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench lines' folder
 for l in $libs; do
-  FEN_HIP_LIB=$l timeout -k 10 200 python bench.py --no-train --no-cpu-baseline --no-stress --steps 30 --warmup 5 > gpurun_out/abops/b.json 2> gpurun_out/abops/b.log || exit 1
-  python -c "import json,sys; d=json.loads(open('gpurun_out/abops/b.json').read().strip().splitlines()[-1]); print(sys.argv[1], d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'])" $(basename $l)
+  FEN_HIP_LIB=$l timeout -k 10 200 python bench.py --full --no-train --no-cpu-baseline --no-stress --steps 30 --warmup 5 > "$OUT/abops_b.json" 2> "$OUT/abops_b.log" || exit 1
+  python -c "import json,sys; d=json.loads(open('$OUT/abops_b.json').read().strip().splitlines()[-1]); print(sys.argv[1], d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'])" $(basename $l)
 done
 if [ "${STAMPS:-0}" = "1" ]; then
   FEN_HIP_LIB=face-super-resolution_amd/csrc/build_stamp/libfen_hip_gsstamp.so timeout -k 10 200 python tools/stamp_strip.py 2>&1 | grep -v amdgpu.ids

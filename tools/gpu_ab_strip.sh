@@ -7,13 +7,14 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_group_strip.py -m gpu -v -s
 rc=$?; echo "strip tests rc=$rc"; grep -E "rel |passed|failed|Error" gpurun_out/gs_tests.log | tail -8
 [ $rc -eq 0 ] || exit 1
 libs="face-super-resolution_amd/src/hip/libfen_hip.so $(ls face-super-resolution_amd/csrc/build_var/libfen_hip_*.so 2>/dev/null)"
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench lines' folder
 for rep in 1 2; do
   for l in $libs; do
-    FEN_HIP_LIB=$l timeout -k 10 200 python bench.py --no-train --no-cpu-baseline --no-stress --steps 30 --warmup 5 > gpurun_out/ab_b.json 2> gpurun_out/ab_b.log
-    rc=$?; [ $rc -eq 0 ] || { echo "bench $l rc=$rc"; tail -5 gpurun_out/ab_b.log; exit $rc; }
-    python - "$l" <<'PY'
+    FEN_HIP_LIB=$l timeout -k 10 200 python bench.py --full --no-train --no-cpu-baseline --no-stress --steps 30 --warmup 5 > "$OUT/ab_b.json" 2> "$OUT/ab_b.log"
+    rc=$?; [ $rc -eq 0 ] || { echo "bench $l rc=$rc"; tail -5 "$OUT/ab_b.log"; exit $rc; }
+    python - "$l" "$OUT" <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/ab_b.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[2] + "/ab_b.json").read().strip().splitlines()[-1])
 r = d["roofline"]
 print(f"{sys.argv[1].split('/')[-1]:32s} {d['value']:9.1f} img/s  kernel {r['kernel_ms']*1e3:7.1f} us  frac {r['frac']:.4f}  bf16 {d['bf16']['value']:9.1f}")
 PY

@@ -5,8 +5,9 @@ export CHAIN=6 REPS=6
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/profc
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench line's folder
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/profc/inf -o run --output-format csv -- \
-    python bench.py --no-train --no-stress --no-cpu-baseline > gpurun_out/profc/inf_bench.log 2>&1
+    python bench.py --full --no-train --no-stress --no-cpu-baseline > "$OUT/profc_inf_bench.log" 2>&1
 echo "inf rc=$?"
 python tools/prof_summary.py stats "$(find gpurun_out/profc/inf -name '*kernel_stats.csv' | head -1)" gpurun_out/profc/inference_kernel_stats.csv
 head -8 gpurun_out/profc/inference_kernel_stats.csv

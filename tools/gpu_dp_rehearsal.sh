@@ -7,12 +7,13 @@ set -e
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench line's folder
 FEN_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 3 --train-steps 3 \
-    --no-perceptual --no-stress > gpurun_out/dp2_bench.json 2> gpurun_out/dp2_bench.log
+    --full --no-perceptual --no-stress > "$OUT/dp2_bench.json" 2> "$OUT/dp2_bench.log"
 echo DP2_OK
 FEN_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port 29518 tools/time_train_eager.py > gpurun_out/dp2_eager.log 2>&1
 echo EAGER_OK
-tail -1 gpurun_out/dp2_bench.json
+tail -1 "$OUT/dp2_bench.json"
 grep ms gpurun_out/dp2_eager.log

@@ -4,11 +4,12 @@ set -e
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/prof
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench lines' folder
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/inf -o run --output-format csv -- \
-    python bench.py --no-train --no-stress --no-cpu-baseline > gpurun_out/prof/inf_bench.log 2>&1
+    python bench.py --full --no-train --no-stress --no-cpu-baseline > "$OUT/prof_inf_bench.log" 2>&1
  echo INF_OK
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/full -o run --output-format csv -- \
-    python bench.py --no-cpu-baseline > gpurun_out/prof/full_bench.log 2>&1
+    python bench.py --full --no-cpu-baseline > "$OUT/prof_full_bench.log" 2>&1
  echo FULL_OK
 timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/prof/fetch -o run --output-format csv -- \
     python tools/pmc_rcab.py > gpurun_out/prof/fetch.log 2>&1
@@ -22,4 +23,4 @@ ALG=$(grep algorithmic_bytes_per_launch gpurun_out/prof/fetch.log | awk '{print 
 python tools/prof_summary.py pmc "$(find gpurun_out/prof/fetch -name '*counter_collection.csv' | head -1)" \
     "$(find gpurun_out/prof/write -name '*counter_collection.csv' | head -1)" gpurun_out/prof/pmc_k_rcab_d.json \
     k_rcab_d "$ALG" "k_rcab_d deferred-gate RCAB (inference form), fp16, B=32, 64x64x64"
-tail -1 gpurun_out/prof/inf_bench.log
+tail -1 "$OUT/prof_inf_bench.log"

@@ -8,5 +8,6 @@ rc=$?; echo "strip tests rc=$rc"; grep -E "rel |PASS|FAIL|passed|failed|Error" g
 FEN_HIP_LIB=face-super-resolution_amd/csrc/build_stamp/libfen_hip_gsstamp.so timeout -k 10 200 python tools/stamp_strip.py > gpurun_out/stamps.txt 2>&1
 rc=$?; echo "stamps rc=$rc"; cat gpurun_out/stamps.txt | grep -v amdgpu.ids
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --no-train --no-cpu-baseline --no-stress --steps 30 --warmup 5 > gpurun_out/bench_strip.json 2> gpurun_out/bench_strip.log
-rc=$?; echo "bench rc=$rc"; tail -1 gpurun_out/bench_strip.json | cut -c1-900
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench line's folder
+timeout -k 10 300 python bench.py --full --no-train --no-cpu-baseline --no-stress --steps 30 --warmup 5 > "$OUT/bench_strip.json" 2> "$OUT/bench_strip.log"
+rc=$?; echo "bench rc=$rc"; tail -1 "$OUT/bench_strip.json" | cut -c1-900

@@ -3,10 +3,11 @@
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/prof3
+OUT=${FEN_OUT:-out}; mkdir -p "$OUT"     # the bench line's folder
 FEN_HIP_LIB=face-super-resolution_amd/csrc/build_stamp/libfen_hip_gsstamp.so timeout -k 10 200 python tools/stamp_strip.py > gpurun_out/prof3/stamps.txt 2>&1
 echo "stamps rc=$?"; cat gpurun_out/prof3/stamps.txt | tail -25
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof3/inf -o run --output-format csv -- \
-    python bench.py --no-train --no-stress --no-cpu-baseline > gpurun_out/prof3/inf_bench.log 2>&1
+    python bench.py --full --no-train --no-stress --no-cpu-baseline > "$OUT/prof3_inf_bench.log" 2>&1
 echo "inf rc=$?"
 python tools/prof_summary.py stats "$(find gpurun_out/prof3/inf -name '*kernel_stats.csv' | head -1)" gpurun_out/prof3/inference_kernel_stats.csv
 head -8 gpurun_out/prof3/inference_kernel_stats.csv
