@@ -190,6 +190,21 @@ static void misc_refusals() {
     EXPECT(fen_ssim_ex(FEN_BF16, 2, 3, 64, 64, nullptr, nullptr, nullptr, 11, 1e-4f, 9e-4f, nullptr, nullptr, 1.f, 2,
                        (float*)fake(0), nullptr) == FEN_EINVAL);
     EXPECT(fen_bicubic_down4(0, 3, 256, 256, nullptr, nullptr, nullptr) == FEN_EINVAL);
+    {   // fen_msssim: every refusal is a host check before the first launch
+        float* f = (float*)fake(0);
+        EXPECT(fen_msssim_work_floats(2, 3, 64, 64, 5) > 0 && fen_msssim_work_floats(2, 3, 16, 16, 5) == 0);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, nullptr, f, f, 11, 1e-4f, 9e-4f, f, 5, f, f, nullptr, 0.f, 0, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, nullptr, 5, f, f, nullptr, 0.f, 0, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 5, nullptr, f, nullptr, 0.f, 0, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 5, f, nullptr, nullptr, 0.f, 0, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 5, f, f, nullptr, 1.f, 1, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 5, f, f, f, 1.f, 3, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_BF16, 2, 4, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 5, f, f, f, 1.f, 2, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 7, 1e-4f, 9e-4f, f, 5, f, f, nullptr, 0.f, 0, nullptr) == FEN_EUNSUPPORTED);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 9, f, f, nullptr, 0.f, 0, nullptr) == FEN_EUNSUPPORTED);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 0, f, f, nullptr, 0.f, 0, nullptr) == FEN_EUNSUPPORTED);
+        EXPECT(fen_msssim(FEN_F32, 2, 3, 16, 16, f, f, f, 11, 1e-4f, 9e-4f, f, 5, f, f, nullptr, 0.f, 0, nullptr) == FEN_EUNSUPPORTED);
+    }
 }
 
 // `asan_check overflow`: hands fen_pack_table a table one job too short -- the library's own

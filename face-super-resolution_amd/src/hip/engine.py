@@ -46,11 +46,12 @@ class FENEngine:
                  device="cuda", loss_weight: float = 1.0, clip: float = 0.5, lr: float = 1e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, process_group=None,
                  perceptual: Optional[dict] = None, ssim_weight: float = 0.0, exchange=None,
-                 adam_state=None, accumulation_steps: int = 1):
+                 adam_state=None, accumulation_steps: int = 1, ms_ssim_weight: float = 0.0):
         """perceptual (training only): the stage configs' VGG19 term (perceptual.py:144-169) as
         dict(weight=, layers=, criterion=, normalize=, params={'features.i.weight': ...},
         layer_weights=None); its gradient joins the fused L1 gradient in dL/dsr.  ssim_weight
-        (training only): the stage-2 term weight * (1 - SSIM) (ssim_loss.py:174-226), likewise.
+        (training only): the stage-2 term weight * (1 - SSIM) (ssim_loss.py:174-226), likewise;
+        ms_ssim_weight (training only): weight * (1 - MS-SSIM) (ssim_loss.py:229-277), likewise.
         exchange (training only): a factory `(flat_grads, bucket_plan) -> obj` with `world`,
         `launch(tag)` and `wait()` replacing the RCCL BucketExchange (the tests' stand-in rank
         pair); the loss gradients are pre-scaled by its `world`.  adam_state (training only): an
@@ -97,6 +98,7 @@ class FENEngine:
             self.l1_weight = loss_weight
             self.ssim_weight = float(ssim_weight)
             self.ssim_val = torch.zeros(1, device=self.device)
+            self.ms_ssim_weight = float(ms_ssim_weight)
             self.vgg = None
             self.loss_perc = torch.zeros(1, device=self.device)
             if perceptual:
@@ -158,6 +160,8 @@ class FENEngine:
                 self.vgg.build(self.x2, self.loss_perc, self.saved_tail["dout"], grad_scale=1.0 / (self.world * self.accum))
             if self.ssim_weight:
                 self._build_ssim()
+            if self.ms_ssim_weight:
+                self._build_ms_ssim()
 
     def _build_ssim(self):
         """weight * (1 - mean SSIM(sr, hr)): the SSIM map's tile sums and its gradient, added
@@ -178,6 +182,23 @@ class FENEngine:
                  ptr(work))
         ctx.emit("ssim_img", ctx.lib.fen_colsum, rows, B, ptr(part), 1.0 / (C * H * W), ptr(per), 0)
         ctx.emit("ssim_mean", ctx.lib.fen_colsum, B, 1, ptr(per), 1.0 / B, ptr(self.ssim_val), 0)
+
+    def _build_ms_ssim(self):
+        """weight * (1 - MS-SSIM(sr, hr)), one scalar for the batch: the value and the per-level
+        means to ms_ssim_out, the gradient added to dL/dsr (NHWC16); one fen_msssim call."""
+        ctx, s = self.ctx, self.spec
+        B, C, H, W = self.B, s.out_ch, self.H, self.W
+        from ..losses.ssim import MS_SSIM_WEIGHTS, _window1d
+        self.ms_ssim_win = _window1d(11, 1.5).to(self.device)
+        self.ms_ssim_w = torch.tensor(MS_SSIM_WEIGHTS, device=self.device)
+        levels = self.ms_ssim_w.numel()
+        if min(H, W) < 2 ** levels:
+            raise ValueError(f"MS-SSIM over {levels} scales needs min(H, W) >= {2 ** levels} (got {H} x {W})")
+        self.ms_ssim_out = torch.zeros(1 + levels, device=self.device)
+        work = ctx.scratch("ms_ssim_work", (int(ctx.lib.fen_msssim_work_floats(B, C, H, W, levels)),), torch.float32)
+        ctx.emit("ms_ssim", ctx.lib.fen_msssim, ctx.code, B, C, H, W, ptr(self.out), ptr(self.hr), ptr(self.ms_ssim_win),
+                 11, 0.01 ** 2, 0.03 ** 2, ptr(self.ms_ssim_w), levels, ptr(work), ptr(self.ms_ssim_out),
+                 ptr(self.saved_tail["dout"]), -self.ms_ssim_weight / (self.world * self.accum), 2)
 
     def _build_backward(self):
         s, ctx = self.spec, self.ctx
@@ -235,14 +256,16 @@ class FENEngine:
         return self.total_loss()
 
     def total_loss(self) -> torch.Tensor:
-        """weight * L1 (+ the weighted perceptual term), on the device."""
-        if self.vgg is None and not self.ssim_weight:
+        """weight * L1 (+ the weighted perceptual, SSIM and MS-SSIM terms), on the device."""
+        if self.vgg is None and not self.ssim_weight and not self.ms_ssim_weight:
             return self.loss if self.l1_weight == 1.0 else self.loss * self.l1_weight
         t = self.loss * self.l1_weight
         if self.vgg is not None:
             t = t + self.loss_perc
         if self.ssim_weight:
             t = t + self.ssim_weight * (1 - self.ssim_val)
+        if self.ms_ssim_weight:
+            t = t + self.ms_ssim_weight * (1 - self.ms_ssim_out[:1])
         return t
 
     def set_lr(self, lr: float):

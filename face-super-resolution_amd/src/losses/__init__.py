@@ -5,8 +5,11 @@ The stage-1 generator step's loss is L1 (combined.py:38-47) + the VGG19 perceptu
 (sign(sr-hr)/N written by the kernel, fen_conv_desc.hr); the perceptual term runs on the
 HIP VGG path (src/hip/vgg.py) and its gradient joins L1's in the same dL/dsr buffer; the
 stage-2 SSIM term (ssim_loss.py:174-226) runs on the HIP SSIM kernel (src/losses/ssim.py,
-fused into the engine's dL/dsr as well).  MS-SSIM / L2 / Charbonnier are outside the built
-path: asking for them raises instead of silently training something else.
+fused into the engine's dL/dsr as well).  MS-SSIM (ssim_loss.py:101-171, 229-277) is built as
+a module (`ms_ssim`, `MSSSIMLoss`: src/losses/ssim.py, csrc/msssim.hip) and as an engine term
+(`FENEngine(ms_ssim_weight=)`), but is not yet selectable through `CombinedLoss`: like L2 /
+Charbonnier (outside the built path), asking `CombinedLoss` for it raises
+instead of silently training something else.
 """
 from __future__ import annotations
 
@@ -144,7 +147,7 @@ def create_loss_function(l1_weight: float = 1.0, perceptual_weight: float = 0.01
 
 
 from .perceptual import PerceptualLoss, VGGFeatureExtractor  # noqa: E402
-from .ssim import MSSSIMLoss, SSIMLoss, ssim  # noqa: E402
+from .ssim import MSSSIMLoss, SSIMLoss, ms_ssim, ssim  # noqa: E402
 
 __all__ = ["LossConfig", "L1Loss", "CombinedLoss", "create_loss_function", "PerceptualLoss", "VGGFeatureExtractor",
-           "SSIMLoss", "MSSSIMLoss", "ssim"]
+           "SSIMLoss", "MSSSIMLoss", "ssim", "ms_ssim"]

@@ -4,8 +4,14 @@
 computation is one fen_ssim launch (csrc/ssim.hip: separable 11-tap Gaussian passes in LDS,
 the SSIM map and its per-tile sums; with a gradient, d(SSIM)/d(pred) in closed form in the
 same launch) plus fixed-order column sums -- no CPU path.  Window 11 only on the kernel (the
-reference's default and the configs' ssim_window_size); MS-SSIM is not built (ms_ssim_weight
-is 0 in every stage config) and raises.
+reference's default and the configs' ssim_window_size).
+
+`ms_ssim` and `MSSSIMLoss` keep the reference's signatures too: one fen_msssim call
+(csrc/msssim.hip: the 2x2 pooling pyramid, per scale the same tiled passes with the
+contrast-structure map and its gradient coefficients, a one-block finish, the pull-back of the
+per-scale gradients to full resolution).  MS-SSIM is built as this module and as an engine term
+(FENEngine(ms_ssim_weight=)); it is not yet selectable through CombinedLoss, which still
+refuses ms_ssim_weight (0 in every stage config).
 """
 from __future__ import annotations
 
@@ -109,13 +115,80 @@ class SSIMLoss(nn.Module):
         return _SSIMFn.apply(pred, target, self.window_size, self.sigma, self.data_range, self.size_average)
 
 
-def ms_ssim(*args, **kwargs):
-    raise NotImplementedError("MS-SSIM is not built on the MI355X path (ms_ssim_weight is 0 in the stage configs)")
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def _ms_weights(weights, device) -> torch.Tensor:
+    if weights is None:
+        weights = MS_SSIM_WEIGHTS
+    w = torch.as_tensor(weights, dtype=torch.float32).detach().reshape(-1).to(device).contiguous()
+    if not 1 <= w.numel() <= 8:
+        raise NotImplementedError(f"the HIP MS-SSIM runs 1 to 8 scales (got {w.numel()} weights)")
+    return w
+
+
+def _ms_run(pred, target, window_size, sigma, data_range, weights, grad_scale=None):
+    """-> (out fp32 [1 + levels] on the device: MS-SSIM, then each level's batch mean (the
+    contrast-structure mean M_i, the SSIM mean at the last level); NCHW fp32 grad_scale *
+    d(MS-SSIM)/dpred or None).  One fen_msssim call (csrc/msssim.hip): nothing comes back to
+    the host."""
+    _check(pred, target, window_size)
+    lib = L.load()
+    B, C, H, W = pred.shape
+    w = _ms_weights(weights, pred.device)
+    levels = w.numel()
+    if min(H, W) < 2 ** levels:
+        raise ValueError(f"MS-SSIM over {levels} scales needs min(H, W) >= {2 ** levels} (got {H} x {W}): the "
+                         f"reference pools once after every scale")
+    p = pred.detach().float().contiguous()
+    t = target.detach().float().contiguous()
+    win = _window1d(window_size, sigma).to(p.device)
+    C1, C2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    work = torch.empty(lib.fen_msssim_work_floats(B, C, H, W, levels), device=p.device)
+    out = torch.empty(1 + levels, device=p.device)
+    grad = torch.empty_like(p) if grad_scale is not None else None
+    L.check(lib.fen_msssim(L.F32, B, C, H, W, ptr(p), ptr(t), ptr(win), window_size, C1, C2, ptr(w), levels, ptr(work),
+                           ptr(out), ptr(grad), 0.0 if grad_scale is None else float(grad_scale),
+                           0 if grad is None else 1, torch.cuda.current_stream().cuda_stream), "msssim")
+    return out, grad
+
+
+def ms_ssim(pred: torch.Tensor, target: torch.Tensor, window_size: int = 11, sigma: float = 1.5,
+            data_range: float = 1.0, weights=None) -> torch.Tensor:
+    """ssim_loss.py:101-171 (a metric: no gradient flows through this function).  One scalar
+    for the batch; len(weights) scales, the last weight unused, as in the reference."""
+    out, _ = _ms_run(pred, target, window_size, sigma, data_range, weights)
+    return out[0].clone()
+
+
+class _MSSSIMFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, pred, target, window_size, sigma, data_range, weights):
+        out, grad = _ms_run(pred, target, window_size, sigma, data_range, weights,
+                            grad_scale=-1.0 if pred.requires_grad else None)
+        fctx.grad = grad
+        return 1 - out[0]
+
+    @staticmethod
+    def backward(fctx, g):
+        return fctx.grad * g, None, None, None, None, None
 
 
 class MSSSIMLoss(nn.Module):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("MS-SSIM is not built on the MI355X path (ms_ssim_weight is 0 in the stage configs)")
+    """1 - MS-SSIM (ssim_loss.py:229-270); gradient w.r.t. pred in closed form on the GPU, in
+    the same call as the value."""
+
+    def __init__(self, window_size: int = 11, sigma: float = 1.5, data_range: float = 1.0, weights=None):
+        super().__init__()
+        self.window_size = window_size
+        self.sigma = sigma
+        self.data_range = data_range
+        if weights is None:
+            weights = torch.tensor(MS_SSIM_WEIGHTS)
+        self.register_buffer('weights', torch.as_tensor(weights, dtype=torch.float32))
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return _MSSSIMFn.apply(pred, target, self.window_size, self.sigma, self.data_range, self.weights)
 
 
 __all__ = ["create_gaussian_window", "ssim", "ms_ssim", "SSIMLoss", "MSSSIMLoss"]

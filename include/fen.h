@@ -605,6 +605,24 @@ int fen_ssim_ex(int dtype, int B, int C, int H, int W, const float* pred, const 
                 const float* window1d, int window_size, float C1, float C2, float* part, void* grad,
                 float grad_scale, int grad_mode, float* work, void* stream);
 
+/* ---- MS-SSIM (src/losses/ssim_loss.py:101-171) ----
+ * levels x_0 = pred / target (NCHW fp32), x_{i+1} = 2x2 average pooling (floor mode); the SSIM
+ * terms above at every level; M_i = the batch mean of the contrast-structure map (2 spt + C2) /
+ * (spp + stt + C2) for i < levels-1, V = the batch mean of the SSIM map at the last level.
+ * out (device, float[1 + levels]): out[0] = V * prod_{i<levels-1} M_i^weights[i], out[1 + i] =
+ * M_i (V at the last level); weights_dev = `levels` device floats (the last one unused, as in
+ * the reference); a negative M_i gives NaN, as there.  grad_mode 1: grad = NCHW fp32 grad_scale
+ * * d(out[0])/d(pred) (written); 2 (C <= 3, dtype fp32 / bf16): that ADDED to channels 0..C-1 of
+ * an NHWC [B,H,W,16] buffer of dtype; 0: none.  work: fen_msssim_work_floats() floats (the pooled
+ * levels, the per-level gradient maps, tile sums and factors).  Pooling, level, finish and
+ * combine launches on `stream`: no atomics, fixed-order sums, no host synchronisation.
+ * FEN_EUNSUPPORTED: window_size != 11, levels outside 1..8, min(H, W) < 2^levels (the reference
+ * fails there too), B * C > 65535; fen_msssim_work_floats returns 0 for those shapes.         */
+size_t fen_msssim_work_floats(int B, int C, int H, int W, int levels);
+int fen_msssim(int dtype, int B, int C, int H, int W, const float* pred, const float* target,
+               const float* window1d, int window_size, float C1, float C2, const float* weights_dev, int levels,
+               float* work, float* out, void* grad, float grad_scale, int grad_mode, void* stream);
+
 /* ---- HR batch preparation (src/data/transforms.py:173-279 + to_tensor 260-279) ----
  * src_u8: B uint8 HWC crops [B,P,P,3] (RGB, P even); params: B records {int flip, int
  * jitter, float brightness, contrast, saturation, int rot90_k} drawn by the host; sums: int64
