@@ -205,6 +205,27 @@ static void misc_refusals() {
         EXPECT(fen_msssim(FEN_F32, 2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, f, 0, f, f, nullptr, 0.f, 0, nullptr) == FEN_EUNSUPPORTED);
         EXPECT(fen_msssim(FEN_F32, 2, 3, 16, 16, f, f, f, 11, 1e-4f, 9e-4f, f, 5, f, f, nullptr, 0.f, 0, nullptr) == FEN_EUNSUPPORTED);
     }
+    {   // fen_image_metrics: likewise
+        float* f = (float*)fake(0);
+        int* ip = (int*)fake(1);
+        EXPECT(fen_image_metrics_work_floats(2, 3, 40, 72) == (size_t)2 * 2 * 3 * 2 * 3);
+        EXPECT(fen_image_metrics_work_floats(0, 3, 64, 64) == 0 && fen_image_metrics_work_floats(2, 3, 64, -1) == 0);
+        EXPECT(fen_image_metrics_work_floats(30000, 3, 64, 64) == 0);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, nullptr, f, f, 11, 1e-4f, 9e-4f, 1.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, nullptr, f, 11, 1e-4f, 9e-4f, 1.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, nullptr, 11, 1e-4f, 9e-4f, 1.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 0, nullptr, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 0, f, nullptr, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 1, f, f, f, 8, nullptr, nullptr, nullptr) == FEN_EINVAL);   // table, no cursor
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 1, f, f, f, 0, ip, nullptr, nullptr) == FEN_EINVAL);        // table_cap 0
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 2, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);   // quantise without clamp
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 255.f, 3, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL); // quantise, range != 1
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 4, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);   // unknown flag
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 0.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_image_metrics(2, 3, 64, 64, f, f, f, 7, 1e-4f, 9e-4f, 1.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EUNSUPPORTED);
+        EXPECT(fen_image_metrics(30000, 3, 64, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EUNSUPPORTED);
+        EXPECT(fen_image_metrics(2, 3, 0, 64, f, f, f, 11, 1e-4f, 9e-4f, 1.f, 0, f, f, nullptr, 0, nullptr, nullptr, nullptr) == FEN_EUNSUPPORTED);
+    }
 }
 
 // `asan_check overflow`: hands fen_pack_table a table one job too short -- the library's own

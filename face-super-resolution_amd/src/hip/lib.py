@@ -198,6 +198,10 @@ _SIGS = {
     "fen_msssim_work_floats": (c_size_t, [c_int] * 5),
     "fen_msssim": (c_int, [c_int] * 5 + [c_void_p] * 3 + [c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p,
                                                           c_void_p, c_float, c_int, c_void_p]),
+    "fen_image_metrics_work_floats": (c_size_t, [c_int] * 4),
+    "fen_image_metrics": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int, c_float, c_float, c_float, c_int, c_void_p,
+                                                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                                                 c_void_p]),
     "fen_augment_u8": (c_int, [c_int, c_int] + [c_void_p] * 5),
     "fen_bn_work_floats": (c_size_t, [c_int]),
     "fen_bn_stats": (c_int, [c_int, c_size_t, c_int, c_void_p, c_float, c_float] + [c_void_p] * 5),

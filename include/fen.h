@@ -623,6 +623,33 @@ int fen_msssim(int dtype, int B, int C, int H, int W, const float* pred, const f
                const float* window1d, int window_size, float C1, float C2, const float* weights_dev, int levels,
                float* work, float* out, void* grad, float grad_scale, int grad_mode, void* stream);
 
+/* ---- Per-image evaluation metrics (src/evaluation/metrics.py: psnr_batch 37-52, SSIM 67-78,
+ * MetricCalculator.evaluate_dataset 171-224) ----
+ * One tile launch over pred / target (NCHW fp32, the SSIM window and constants as above) reads
+ * each once and leaves, per 32x32 tile of each plane, the SSIM-map sum and the squared-error sum
+ * over the tile's own pixels in work (fen_image_metrics_work_floats() floats); a one-block finish
+ * reduces them per image in a fixed order (no atomics: two runs are bit-identical) to
+ * out[3][B] (device): out[0][b] = mse = sse / (C H W), out[1][b] = 10 log10(data_range^2 /
+ * (mse + 1e-10)) in dB, out[2][b] = the mean of the SSIM map.
+ * flags, applied to pred in registers as it is loaded (the SSE and the SSIM both see the result):
+ * bit 0 clamps to [0, data_range]; bit 1 quantises to 8 bits, floor(x * 255) / 255 with the
+ * product one round-to-nearest fp32 multiply (np.clip(x * 255, 0, 255).astype(uint8) / 255);
+ * bit 1 needs bit 0 and data_range == 1.
+ * table (or NULL): device float[2][table_cap], a dataset-long record.  The finish reads n =
+ * nvalid ? *nvalid : B (limited to 0..B) and c = *cursor (device ints), writes images 0..n-1 to
+ * table[0][c + i] (PSNR) and table[1][c + i] (SSIM) for c + i < table_cap only, and sets *cursor
+ * = c + n even past table_cap, so the host sees an overflow.  Offset and count live in device
+ * memory: one captured launch pair serves every batch of a dataset, a partial last one included.
+ * FEN_EINVAL: a NULL pred / target / window1d / work / out, table without cursor or with
+ * table_cap <= 0, unknown flag bits, bit 1 without bit 0 or with data_range != 1, data_range <=
+ * 0.  FEN_EUNSUPPORTED: window_size != 11, a non-positive dimension, B * C > 65535 (one block per
+ * tile and plane), C H W > 2^31; fen_image_metrics_work_floats returns 0 for those shapes.     */
+size_t fen_image_metrics_work_floats(int B, int C, int H, int W);
+int fen_image_metrics(int B, int C, int H, int W, const float* pred, const float* target,
+                      const float* window1d, int window_size, float C1, float C2, float data_range, int flags,
+                      float* work, float* out, float* table, int table_cap, int* cursor, const int* nvalid,
+                      void* stream);
+
 /* ---- HR batch preparation (src/data/transforms.py:173-279 + to_tensor 260-279) ----
  * src_u8: B uint8 HWC crops [B,P,P,3] (RGB, P even); params: B records {int flip, int
  * jitter, float brightness, contrast, saturation, int rot90_k} drawn by the host; sums: int64
