@@ -228,6 +228,60 @@ static void misc_refusals() {
     }
 }
 
+// fen_rrdb_conv / fen_rrdb_block / fen_rrdb_first: every refusal is decided on the host, before
+// any launch
+static void rrdb_refusals() {
+    EXPECT(fen_rrdb_conv(nullptr, nullptr) == FEN_EINVAL);
+    fen_rrdb_conv_desc d;
+    std::memset(&d, 0, sizeof d);
+    d.dtype = FEN_F16, d.B = 1, d.H = 8, d.W = 8, d.Cin = 64, d.Cout = 32;
+    d.x = d.y = fake(0), d.w = fake(1), d.bias = (const float*)fake(2);
+    d.x_stride = d.y_stride = 192, d.y_off = 32;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EINVAL);                    // in place inside the read range
+    d.y = fake(3), d.Cin = 80;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EUNSUPPORTED);
+    d.Cin = 64, d.Cout = 48;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EUNSUPPORTED);
+    d.Cout = 32, d.x_stride = 60;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EINVAL);
+    d.x_stride = 192, d.B = 1 << 11, d.H = 1 << 10, d.W = 1 << 10;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EUNSUPPORTED);              // 2^31 pixels
+    d.B = 1, d.H = 7, d.W = 8, d.up2 = 1;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EINVAL);
+    d.up2 = 0, d.dtype = 9;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EINVAL);
+    d.dtype = FEN_F32, d.bias = nullptr;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EINVAL);
+    d.bias = (const float*)fake(2), d.x = (const char*)fake(0) + 8;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EINVAL);                    // not 16-B aligned
+    d.x = fake(0), d.nchw_out = 1, d.Cout = 17;
+    EXPECT(fen_rrdb_conv(&d, nullptr) == FEN_EUNSUPPORTED);
+
+    EXPECT(fen_rrdb_block(nullptr, nullptr) == FEN_EINVAL);
+    fen_rrdb_block_desc b;
+    std::memset(&b, 0, sizeof b);
+    b.dtype = FEN_BF16, b.B = 1, b.H = 8, b.W = 8, b.num_feat = 64, b.num_grow_ch = 16;
+    b.buf = fake(0), b.next = fake(1);
+    for (int k = 0; k < 5; ++k) b.w[k] = fake(2), b.bias[k] = (const float*)fake(3);
+    EXPECT(fen_rrdb_block(&b, nullptr) == FEN_EUNSUPPORTED);
+    b.num_feat = 32, b.num_grow_ch = 32;
+    EXPECT(fen_rrdb_block(&b, nullptr) == FEN_EUNSUPPORTED);
+    b.num_feat = 64, b.next = b.buf;
+    EXPECT(fen_rrdb_block(&b, nullptr) == FEN_EINVAL);
+    b.next = fake(1), b.x_rrdb = b.next;
+    EXPECT(fen_rrdb_block(&b, nullptr) == FEN_EINVAL);
+    b.x_rrdb = nullptr, b.bias[4] = nullptr;
+    EXPECT(fen_rrdb_block(&b, nullptr) == FEN_EINVAL);
+    b.bias[4] = (const float*)fake(3), b.W = 0;
+    EXPECT(fen_rrdb_block(&b, nullptr) == FEN_EINVAL);
+
+    const float* f = (const float*)fake(0);
+    EXPECT(fen_rrdb_first(FEN_F32, 1, 3, 8, 8, nullptr, f, f, fake(1), 192, nullptr, nullptr) == FEN_EINVAL);
+    EXPECT(fen_rrdb_first(FEN_F32, 1, 3, 8, 8, f, f, f, fake(1), 48, nullptr, nullptr) == FEN_EINVAL);
+    EXPECT(fen_rrdb_first(FEN_F32, 0, 3, 8, 8, f, f, f, fake(1), 192, nullptr, nullptr) == FEN_EINVAL);
+    EXPECT(fen_rrdb_first(FEN_F32, 1, 9, 8, 8, f, f, f, fake(1), 192, nullptr, nullptr) == FEN_EUNSUPPORTED);
+}
+
 // `asan_check overflow`: hands fen_pack_table a table one job too short -- the library's own
 // write past it must be caught (proves the host half of libfen_hip_asan.so is instrumented)
 static int overflow_selftest() {
@@ -250,6 +304,7 @@ int main(int argc, char** argv) {
     chain_tables();
     status_and_rccl();
     misc_refusals();
+    rrdb_refusals();
     if (g_fail) {
         std::fprintf(stderr, "asan_check: %d expectation(s) failed\n", g_fail);
         return 1;

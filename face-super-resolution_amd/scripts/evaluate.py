@@ -2,15 +2,18 @@
 """Evaluate a checkpoint: per-image PSNR / SSIM over a validation set on the HIP path.
 
     python scripts/evaluate.py --checkpoint X.pth [--data-root DIR | --synthetic N] \\
-        [--batch-size 32] [--precision fp16|bf16|fp32] [--quantize] [--json OUT]
+        [--batch-size 32] [--precision fp16|bf16|fp32] [--quantize] [--json OUT] [--model custom|esrgan]
 
 The checkpoint is loaded weights-only (FaceEnhanceNet.from_pretrained); the images come from
 get_dataloader(mode='val') -- the full images, in order, the last batch partial -- and LR is
 synthesised from HR on the GPU as in training.  MetricCalculator.evaluate_dataset runs the
 captured inference engine and one fused metrics call per batch, with one host read at the end.
 --quantize rounds SR to 8 bits first, as the reference's scripts/test_model.py does before it
-measures.  Prints psnr_mean / psnr_std / ssim_mean / ssim_std / num_images; --json OUT writes
-them with the per-image arrays.
+measures.  --model esrgan evaluates the ESRGAN comparison baseline instead (a 23-block RRDBNet;
+--checkpoint is its state dict -- plain, or under 'params_ema' / 'params' -- or absent for random
+weights with a warning): the same loader, LR synthesis and fused fen_image_metrics call per batch,
+the forward run eagerly at whatever size the images have.  Prints psnr_mean / psnr_std /
+ssim_mean / ssim_std / num_images; --json OUT writes them with the per-image arrays.
 """
 import argparse
 import json
@@ -23,7 +26,11 @@ sys.path.insert(0, str(PKG))
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="PSNR / SSIM of a FaceEnhanceNet checkpoint over a validation set")
-    ap.add_argument("--checkpoint", required=True, help="a reference-format .pth checkpoint")
+    ap.add_argument("--model", choices=["custom", "esrgan"], default="custom",
+                    help="custom: FaceEnhanceNet (default); esrgan: the RRDBNet baseline")
+    ap.add_argument("--checkpoint", default=None,
+                    help="a reference-format .pth checkpoint (required for --model custom; esrgan: a RRDBNet "
+                         "state dict, or none for random weights)")
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--data-root", default=None, help="a directory of HxWx3 .npy images (or DIR/val)")
     src.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded synthetic HR images instead")
@@ -34,7 +41,59 @@ def parse_args(argv=None):
                     help="the compute precision (default: the checkpoint's config, else fp32)")
     ap.add_argument("--quantize", action="store_true", help="quantise SR to 8 bits before measuring")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the results and per-image arrays here")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.model == "custom" and not args.checkpoint:
+        ap.error("the following arguments are required: --checkpoint")
+    return args
+
+
+def evaluate_esrgan(args, loader):
+    """The baseline over `loader`: per batch LR = fen_bicubic_down4(HR) (or the batch's 'lr'), one
+    RRDBNet forward, one fen_image_metrics call on the clamped (--quantize: 8-bit) SR; the
+    per-image numbers stay on the device until one read at the end.  The statistics are
+    MetricCalculator.evaluate_dataset's: PSNR over images, SSIM over per-batch means."""
+    import warnings
+
+    import numpy as np
+    import torch
+
+    from src.evaluation.metrics import FLAG_CLAMP, FLAG_QUANTIZE, image_metrics
+    from src.hip import lib as L
+    from src.models import RRDBNet
+    model = RRDBNet(precision=args.precision or "fp32")
+    if args.checkpoint:
+        state = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
+        for key in ("params_ema", "params"):
+            if isinstance(state, dict) and key in state:
+                state = state[key]
+                break
+        model.load_state_dict(state, strict=False)
+    else:
+        warnings.warn("--model esrgan without --checkpoint: randomly initialised weights (for testing only)")
+    model = model.to("cuda").eval()
+    flags = FLAG_CLAMP | (FLAG_QUANTIZE if args.quantize else 0)
+    lib = L.load()
+    outs = []
+    with torch.no_grad():
+        for batch in loader:
+            hr = batch["hr"].to("cuda").float().contiguous()
+            lr = batch.get("lr")
+            B, C, H, W = (int(v) for v in hr.shape)
+            if lr is None:
+                if H % 4 or W % 4:
+                    raise ValueError(f"HR {H} x {W} is not a multiple of the scale factor 4")
+                lr = torch.empty(B, C, H // 4, W // 4, device="cuda")
+                L.check(lib.fen_bicubic_down4(B, C, H, W, hr.data_ptr(), lr.data_ptr(),
+                                              torch.cuda.current_stream().cuda_stream), "bicubic_down4")
+            outs.append(image_metrics(model(lr.to("cuda")), hr, 1.0, flags).clone())
+    if not outs:
+        raise ValueError("evaluate.py: the dataloader yielded no batch")
+    host = [o.cpu().double().numpy() for o in outs]          # the one wait for the stream
+    ps = np.concatenate([o[1] for o in host])
+    ss = np.concatenate([o[2] for o in host])
+    batch_ssim = np.array([o[2].mean() for o in host])
+    return {"psnr_mean": float(ps.mean()), "psnr_std": float(ps.std()), "ssim_mean": float(batch_ssim.mean()),
+            "ssim_std": float(batch_ssim.std()), "per_image": {"psnr": ps, "ssim": ss}, "num_images": int(ps.size)}
 
 
 def main(argv=None) -> int:
@@ -49,6 +108,18 @@ def main(argv=None) -> int:
         raise SystemExit("evaluate.py: give --data-root DIR or --synthetic N")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py: the HIP path needs a ROCm GPU")
+    if args.model == "esrgan":
+        loader = get_dataloader(args.data_root, mode="val", batch_size=args.batch_size, num_workers=args.num_workers,
+                                hr_patch_size=args.hr_size, synthetic=args.synthetic, device="cpu")
+        res = evaluate_esrgan(args, loader)
+        per = res.pop("per_image")
+        res.update(model="esrgan", checkpoint=str(args.checkpoint), precision=args.precision or "fp32",
+                   quantize=bool(args.quantize))
+        print(json.dumps(res))
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(dict(res, per_image={k: [float(v) for v in a] for k, a in per.items()}), f)
+        return 0
     model = FaceEnhanceNet.from_pretrained(args.checkpoint)
     if args.precision is not None and args.precision != model.config.precision:
         cfg = model.config

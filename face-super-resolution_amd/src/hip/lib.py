@@ -120,6 +120,23 @@ class RcabC128Desc(Structure):
     ]
 
 
+class RrdbConvDesc(Structure):      # fen_rrdb_conv_desc
+    _fields_ = [
+        ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
+        ("x", c_void_p), ("x_stride", c_int), ("up2", c_int), ("w", c_void_p), ("bias", c_void_p),
+        ("y", c_void_p), ("y_stride", c_int), ("y_off", c_int), ("lrelu", c_int),
+        ("r1", c_void_p), ("r1_stride", c_int), ("s1", c_float),
+        ("r2", c_void_p), ("r2_stride", c_int), ("s2", c_float), ("nchw_out", c_int),
+    ]
+
+
+class RrdbBlockDesc(Structure):     # fen_rrdb_block_desc
+    _fields_ = [
+        ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("num_feat", c_int), ("num_grow_ch", c_int),
+        ("buf", c_void_p), ("next", c_void_p), ("x_rrdb", c_void_p), ("w", c_void_p * 5), ("bias", c_void_p * 5),
+    ]
+
+
 class WgradDesc(Structure):
     _fields_ = [
         ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
@@ -202,6 +219,9 @@ _SIGS = {
     "fen_image_metrics": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int, c_float, c_float, c_float, c_int, c_void_p,
                                                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                                                  c_void_p]),
+    "fen_rrdb_conv": (c_int, [POINTER(RrdbConvDesc), c_void_p]),
+    "fen_rrdb_block": (c_int, [POINTER(RrdbBlockDesc), c_void_p]),
+    "fen_rrdb_first": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
     "fen_augment_u8": (c_int, [c_int, c_int] + [c_void_p] * 5),
     "fen_bn_work_floats": (c_size_t, [c_int]),
     "fen_bn_stats": (c_int, [c_int, c_size_t, c_int, c_void_p, c_float, c_float] + [c_void_p] * 5),

@@ -650,6 +650,67 @@ int fen_image_metrics(int B, int C, int H, int W, const float* pred, const float
                       float* work, float* out, float* table, int table_cap, int* cursor, const int* nvalid,
                       void* stream);
 
+/* ---- ESRGAN baseline, RRDBNet (src/models/esrgan.py:17-103), inference only ----
+ * 3x3 / pad 1 convs over a growing channel concatenation (csrc/rrdb.hip).  A ResidualDenseBlock
+ * (esrgan.py:85-103) lives in one NHWC buffer of 192 channels per pixel, x | x1 | x2 | x3 | x4
+ * (torch.cat's order): conv k reads channels [0, 64 + 32 (k - 1)) at pixel stride 192 and writes
+ * its own slice; no concatenation is copied and no elementwise launch sits between convs.
+ *
+ * fen_rrdb_conv: one launch.  v = conv(x[..., 0:Cin]; w) + bias; lrelu: LeakyReLU(0.2);
+ * r1: v = v * s1 + r1[..., 0:Cout]; r2: v = v * s2 + r2[..., 0:Cout] (each product rounded before
+ * its sum); y[..., y_off : y_off + Cout] = v in dtype, or with nchw_out y = NCHW fp32 [B,Cout,H,W].
+ * B, H, W are the OUTPUT's; up2 = 1 (H, W even): the input is [B,H/2,W/2,x_stride] and the tap
+ * at output position (i, j) reads input pixel (i >> 1, j >> 1) -- nearest x2 upsampling fused
+ * into the gather (esrgan.py:60-63).  Strides and offsets in elements.  w: fen_pack_conv_w mode
+ * 0, [9][Cout_pad][Cin].  Any H, W >= 1 (ragged tiles are masked).  y may be x itself only when
+ * the written slice starts at or past Cin (read and written channel ranges disjoint), else
+ * FEN_EINVAL; y may not otherwise overlap x.  FEN_EINVAL: NULL x / w / bias / y, non-positive
+ * dimensions, pointers not 16-B aligned, strides too small or not whole 16-B chunks, odd H / W
+ * with up2.  FEN_EUNSUPPORTED: Cin not 64 + 32 j (j = 0..4), Cout not 32 / 64 (nchw_out: > 16),
+ * B * H * W >= 2^31 (the kernels' pixel indices).                                              */
+typedef struct {
+    int dtype;                 /* fen_dtype of x, w, y, r1, r2                                  */
+    int B, H, W;               /* output geometry                                               */
+    int Cin, Cout;
+    const void* x;             /* NHWC, pixel stride x_stride >= Cin                            */
+    int x_stride;
+    int up2;
+    const void* w;
+    const float* bias;         /* [Cout]                                                        */
+    void* y;
+    int y_stride, y_off;
+    int lrelu;
+    const void* r1;            /* NHWC at pixel stride r1_stride (channels 0..Cout-1), or NULL  */
+    int r1_stride;
+    float s1;
+    const void* r2;
+    int r2_stride;
+    float s2;
+    int nchw_out;
+} fen_rrdb_conv_desc;
+int fen_rrdb_conv(const fen_rrdb_conv_desc* d, void* stream);
+/* A whole ResidualDenseBlock, five launches: conv 1..4 fill buf's slices 64.. (bias + LeakyReLU),
+ * conv5 writes (conv5 + bias) * 0.2 + x -- with x_rrdb (the RRDB's input, channels 0..63 of its
+ * first block's buffer; esrgan.py:78-82) that * 0.2 + x_rrdb -- into channels 0..63 of `next`,
+ * the following block's buffer.  buf, next, x_rrdb: NHWC [B,H,W,192] of dtype; next is neither
+ * buf nor x_rrdb.  FEN_EUNSUPPORTED: num_feat != 64 or num_grow_ch != 32.                      */
+typedef struct {
+    int dtype;
+    int B, H, W;
+    int num_feat, num_grow_ch;
+    void* buf;
+    void* next;
+    const void* x_rrdb;        /* NULL for an RRDB's first two blocks                           */
+    const void* w[5];          /* conv1..conv5 packed mode 0                                    */
+    const float* bias[5];
+} fen_rrdb_block_desc;
+int fen_rrdb_block(const fen_rrdb_block_desc* d, void* stream);
+/* conv_first (esrgan.py:36,55): x NCHW fp32 [B,Ci,H,W], w OIHW fp32 [64,Ci,3,3] -> channels 0..63
+ * of y (NHWC of dtype at pixel stride y_stride >= 64) and, when y2 != NULL, the same values to a
+ * dense NHWC [B,H,W,64] y2 (the feat of `feat + body_feat`).  Ci <= 8.                         */
+int fen_rrdb_first(int dtype, int B, int Ci, int H, int W, const float* x, const float* w, const float* bias,
+                   void* y, int y_stride, void* y2, void* stream);
+
 /* ---- HR batch preparation (src/data/transforms.py:173-279 + to_tensor 260-279) ----
  * src_u8: B uint8 HWC crops [B,P,P,3] (RGB, P even); params: B records {int flip, int
  * jitter, float brightness, contrast, saturation, int rot90_k} drawn by the host; sums: int64
