@@ -282,6 +282,114 @@ static void rrdb_refusals() {
     EXPECT(fen_rrdb_first(FEN_F32, 1, 9, 8, 8, f, f, f, fake(1), 192, nullptr, nullptr) == FEN_EUNSUPPORTED);
 }
 
+// every entry point that takes a dtype refuses a code that is no fen_dtype with FEN_EINVAL before
+// any launch (tests/test_abi.py holds the same calls)
+static void unknown_dtype_refusals() {
+    void* p = fake(0);
+    float* f = (float*)fake(0);
+    const float win[11] = {0.f};
+    for (int dt : {3, -1}) {
+        fen_conv_desc c;
+        std::memset(&c, 0, sizeof c);
+        c.dtype = dt, c.B = 1, c.H = 16, c.W = 16, c.Cin = 64, c.Cout = 64, c.x = c.w = c.y = p;
+        EXPECT(fen_conv3x3(&c, nullptr) == FEN_EINVAL);
+        fen_wgrad_desc wg[2];
+        std::memset(wg, 0, sizeof wg);
+        for (auto& w : wg) {
+            w.dtype = dt, w.B = 1, w.H = 16, w.W = 16, w.Cin = 64, w.Cout = 64, w.cout_valid = 64;
+            w.x = w.dy = p, w.dw = w.work = f;
+        }
+        EXPECT(fen_wgrad3x3(&wg[0], nullptr) == FEN_EINVAL);
+        EXPECT(fen_wgrad3x3_multi(2, wg, nullptr) == FEN_EINVAL);
+        fen_rcab_deferred_desc r;
+        std::memset(&r, 0, sizeof r);
+        r.dtype = dt, r.B = 1, r.H = 16, r.W = 16, r.C = 64, r.Cr = 16;
+        r.x = r.w1 = r.w2 = r.t = p, r.b1 = r.b2 = r.alpha = f, r.part = f;
+        EXPECT(fen_rcab_deferred(&r, nullptr) == FEN_EINVAL);
+        r.tp = p, r.pp = r.pfc1 = r.pfc2 = f;
+        EXPECT(fen_rcab_group_end(&r, p, f, p, p, nullptr) == FEN_EINVAL);
+        fen_rcab_bwd_desc rb;
+        std::memset(&rb, 0, sizeof rb);
+        rb.dtype = dt, rb.B = 1, rb.H = 16, rb.W = 16, rb.C = 64;
+        rb.dt = rb.w2t = rb.w1t = rb.z1 = p, rb.dy = p, rb.alpha = f, rb.dz1 = rb.dx = p, rb.dalpha_part = f;
+        EXPECT(fen_rcab_bwd(&rb, nullptr) == FEN_EINVAL);
+        std::vector<fen_group_strip_desc> gs(2);
+        for (int g = 0; g < 2; ++g) {
+            fen_group_strip_desc& d = gs[g];
+            std::memset(&d, 0, sizeof d);
+            d.dtype = dt, d.B = 1, d.H = 64, d.W = 64, d.C = 64, d.Cr = 16, d.nb = 1, d.res_scale = 0.2f;
+            d.x = fake(g + 1), d.y = fake(g + 2);
+            d.w1[0] = d.w2[0] = p, d.b1[0] = d.b2[0] = d.alpha[0] = d.fc1[0] = d.fc2[0] = f;
+            d.wg = p, d.bg = f, d.work = fake(400), d.work_bytes = fen_group_strip_chain_work_bytes(1, 64, 2);
+        }
+        EXPECT(fen_group_strip(&gs[0], nullptr) == FEN_EINVAL);
+        EXPECT(fen_group_strip_chain_prepare(gs.data(), 2, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_group_strip_chain(gs.data(), 2, nullptr, nullptr) == FEN_EINVAL);
+        fen_group_strip_bwd_desc gb;
+        std::memset(&gb, 0, sizeof gb);
+        gb.dtype = dt, gb.B = 1, gb.H = 64, gb.W = 64, gb.C = 64, gb.Cr = 16, gb.nb = 1, gb.res_scale = 0.2f;
+        gb.dy = fake(1), gb.dx = fake(2), gb.wgt = p, gb.work = fake(400);
+        gb.work_bytes = fen_group_strip_bwd_work_bytes(1, 64);
+        gb.w1t[0] = gb.w2t[0] = gb.z1[0] = gb.t[0] = gb.a1[0] = p, gb.dt[0] = gb.dz1[0] = p;
+        gb.alpha[0] = gb.fc1[0] = gb.fc2[0] = gb.s[0] = gb.mean[0] = gb.hid[0] = f;
+        gb.dalpha_part[0] = gb.dw1p[0] = gb.dw2p[0] = f;
+        EXPECT(fen_group_strip_bwd(&gb, nullptr) == FEN_EINVAL);
+        fen_rcab_c128_desc c128;
+        std::memset(&c128, 0, sizeof c128);
+        c128.dtype = dt, c128.B = 1, c128.H = 16, c128.W = 16, c128.C = 128, c128.Cr = 16, c128.mode = 3;
+        c128.x = c128.w = c128.res = fake(1), c128.bias = f, c128.y = fake(2);
+        EXPECT(fen_rcab_c128(&c128, nullptr) == FEN_EINVAL);
+        fen_rrdb_conv_desc rc;
+        std::memset(&rc, 0, sizeof rc);
+        rc.dtype = dt, rc.B = 1, rc.H = 8, rc.W = 8, rc.Cin = 64, rc.Cout = 32;
+        rc.x = rc.w = fake(1), rc.bias = f, rc.y = fake(2), rc.x_stride = rc.y_stride = 192, rc.y_off = 64;
+        EXPECT(fen_rrdb_conv(&rc, nullptr) == FEN_EINVAL);
+        fen_rrdb_block_desc blk;
+        std::memset(&blk, 0, sizeof blk);
+        blk.dtype = dt, blk.B = 1, blk.H = 8, blk.W = 8, blk.num_feat = 64, blk.num_grow_ch = 32;
+        blk.buf = fake(1), blk.next = fake(2);
+        for (int k = 0; k < 5; ++k) blk.w[k] = p, blk.bias[k] = f;
+        EXPECT(fen_rrdb_block(&blk, nullptr) == FEN_EINVAL);
+        EXPECT(fen_rrdb_first(dt, 1, 3, 16, 16, f, f, f, p, 192, nullptr, nullptr) == FEN_EINVAL);
+        EXPECT(fen_conv_first_fwd(dt, 1, 3, 16, 16, 64, f, f, f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_conv_first_fwd_ex(dt, 1, 3, 16, 16, 64, f, f, f, f, f, 0.2f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_conv_first_wgrad(dt, 1, 3, 16, 16, 64, f, p, f, f, 0, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_conv_last_dgrad(dt, 1, 16, 16, 64, 3, p, f, p, p, f, p, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_conv_last_bwd(dt, 1, 16, 16, 64, 3, p, f, p, p, f, p, f, f, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_se_fused(dt, 1, 256, 64, 16, 4, 1.f / 256, f, f, f, f, f, f, p, 0.2f, p, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_se_apply(dt, 1, 256, 64, p, f, 0.2f, p, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_pool_dot(dt, 1, 256, 64, p, p, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_se_bwd_fused(dt, 1, 256, 64, 16, 4, 1.f / 256, 0.2f, f, f, f, f, f, f, p, f, f, f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_se_bwd_apply(dt, 1, 256, 64, p, f, 0.2f, f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_pack_conv_w(dt, 0, 64, 64, f, p, nullptr) == FEN_EINVAL);
+        {
+            fen_pack_job job{f, p, 0, 64, 64};
+            std::vector<char> tab(fen_pack_table_bytes(1));
+            size_t total = 0;
+            EXPECT(fen_pack_table(dt, 1, &job, tab.data(), &total) == FEN_EINVAL);
+        }
+        EXPECT(fen_pack_multi(dt, 1, p, 256, nullptr) == FEN_EINVAL);
+        EXPECT(fen_nchw_to_nhwc(dt, 1, 3, 16, 16, 8, f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_nhwc_to_nchw(dt, 1, 3, 16, 16, p, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_prelu_bwd_unshuffle(dt, 1, 16, 16, 64, p, p, f, p, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_maxpool2(dt, 1, 16, 16, 64, p, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_maxpool2_bwd_relu(dt, 1, 16, 16, 64, p, p, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_feat_loss(dt, 64, p, 0, 1.f, p, 0, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_ssim(dt, 1, 3, 16, 16, f, f, win, 11, 1e-4f, 9e-4f, f, p, 1.f, 2, nullptr) == FEN_EINVAL);
+        EXPECT(fen_ssim_ex(dt, 1, 3, 16, 16, f, f, win, 11, 1e-4f, 9e-4f, f, p, 1.f, 2, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_msssim(dt, 1, 3, 32, 32, f, f, win, 11, 1e-4f, 9e-4f, f, 2, f, f, p, 1.f, 1, nullptr) == FEN_EINVAL);
+        EXPECT(fen_bn_stats(dt, 64, 64, p, 1e-5f, 0.1f, f, nullptr, nullptr, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_bn_stats_n(dt, 2, 64, 64, p, 1e-5f, 0.1f, f, nullptr, nullptr, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_bn_apply(dt, 64, 64, p, f, f, f, f, 0.2f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_bn_apply_n(dt, 2, 64, 64, p, f, f, 64, f, f, 0.2f, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_bn_bwd(dt, 64, 64, p, p, f, f, f, 0.2f, p, f, f, 0, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_bn_bwd_n(dt, 2, 64, 64, p, p, f, f, f, 0.2f, p, f, f, 0, f, nullptr) == FEN_EINVAL);
+        EXPECT(fen_subsample2(dt, 1, 16, 16, 64, p, p, nullptr) == FEN_EINVAL);
+        EXPECT(fen_s2d2(dt, 1, 16, 16, 64, p, p, 0, nullptr) == FEN_EINVAL);
+        EXPECT(fen_zero_insert2(dt, 1, 8, 8, 64, p, p, nullptr) == FEN_EINVAL);
+    }
+}
+
 // `asan_check overflow`: hands fen_pack_table a table one job too short -- the library's own
 // write past it must be caught (proves the host half of libfen_hip_asan.so is instrumented)
 static int overflow_selftest() {
@@ -305,6 +413,7 @@ int main(int argc, char** argv) {
     status_and_rccl();
     misc_refusals();
     rrdb_refusals();
+    unknown_dtype_refusals();
     if (g_fail) {
         std::fprintf(stderr, "asan_check: %d expectation(s) failed\n", g_fail);
         return 1;

@@ -1444,43 +1444,12 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3_v(const fen_conv_desc d) {
     }
 }
 
-int g_num_cus = 0;
-
-// kernel-variant selector for A/B runs (FEN_CONV_VARIANT): 0 default (ping-pong persistent
-// kernel k_conv3x3_g for the network's epilogue modes), 1 streamed kernel everywhere,
-// 2 single-group persistent kernel with the generic (runtime-mode) epilogue, 5 single-group
-// persistent kernel k_conv3x3_p with per-mode epilogues
-int conv_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FEN_CONV_VARIANT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
 template <typename T, int COT, int WR, int WC, int EPIC>
 int launch_p(const fen_conv_desc* d, hipStream_t s) {
-    const int tpi = ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
-    const int ntiles = d->B * tpi;
-    const int ncot = ((d->Cout + 15) & ~15) / COT;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_num_cus <= 0) g_num_cus = 256;
-    }
-    int grid = g_num_cus;
-    grid -= grid % ncot;
-    const int maxg = ntiles * ncot;
-    if (grid > maxg) grid = maxg;
+    const int ntiles = d->B * ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
+    const int grid = fen_detail::persistent_grid(ntiles, ((d->Cout + 15) & ~15) / COT);
     const size_t lds = 9 * COT * 128 + 2 * HALO_SLOT + WR * COT * 4 + 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_conv3x3_p<T, COT, WR, WC, EPIC>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    fen_detail::opt_in_lds<k_conv3x3_p<T, COT, WR, WC, EPIC>>((int)lds);
     hipLaunchKernelGGL((k_conv3x3_p<T, COT, WR, WC, EPIC>), dim3(grid), dim3(64 * WR * WC), lds, s, *d);
     FEN_CHECK_LAUNCH();
     return FEN_OK;
@@ -1488,24 +1457,9 @@ int launch_p(const fen_conv_desc* d, hipStream_t s) {
 
 template <typename T, int EPIC>
 int launch_g(const fen_conv_desc* d, hipStream_t s) {
-    const int tpi = ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
-    const int ntiles = d->B * tpi;
-    const int ncot = d->Cout / 64;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_num_cus <= 0) g_num_cus = 256;
-    }
-    int grid = g_num_cus;
-    grid -= grid % ncot;
-    const int maxg = ntiles * ncot;
-    if (grid > maxg) grid = maxg;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_conv3x3_g<T, EPIC>, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-        attr_set = true;
-    }
+    const int ntiles = d->B * ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
+    const int grid = fen_detail::persistent_grid(ntiles, d->Cout / 64);
+    fen_detail::opt_in_lds<k_conv3x3_g<T, EPIC>>(G_LDS);
     hipLaunchKernelGGL((k_conv3x3_g<T, EPIC>), dim3(grid), dim3(512), G_LDS, s, *d);
     FEN_CHECK_LAUNCH();
     return FEN_OK;
@@ -1513,25 +1467,10 @@ int launch_g(const fen_conv_desc* d, hipStream_t s) {
 
 template <typename T, int EPIC>
 int launch_v(const fen_conv_desc* d, hipStream_t s) {
-    const int tpi = ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
-    const int ntiles = d->B * tpi;
+    const int ntiles = d->B * ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
     const int ncot = d->Cout / V_COT;
-    if (g_num_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_num_cus <= 0) g_num_cus = 256;
-    }
-    int grid = g_num_cus;
-    grid -= grid % ncot;
-    if (grid < ncot) grid = ncot;
-    const int maxg = ntiles * ncot;
-    if (grid > maxg) grid = maxg;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_conv3x3_v<T, EPIC>, hipFuncAttributeMaxDynamicSharedMemorySize, V_LDS);
-        attr_set = true;
-    }
+    const int grid = fen_detail::persistent_grid(ntiles, ncot, ncot);   // (at least one block per channel tile)
+    fen_detail::opt_in_lds<k_conv3x3_v<T, EPIC>>(V_LDS);
     hipLaunchKernelGGL((k_conv3x3_v<T, EPIC>), dim3(grid), dim3(512), V_LDS, s, *d);
     FEN_CHECK_LAUNCH();
     return FEN_OK;
@@ -1548,15 +1487,7 @@ bool conv_v_ok(const fen_conv_desc* d) {
     // (and enough 16 x 16 x 128 work items to fill the CUs: a long K loop on a quarter of the
     // chip lost to the streamed kernel's 2-blocks-per-CU grid -- the discriminator's 16 x 16 layers)
     const int items = d->B * ((d->H + 15) >> 4) * ((d->W + 15) >> 4) * (d->Cout / V_COT);
-    int ncu = g_num_cus;
-    if (ncu == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (ncu <= 0) ncu = 256;
-        g_num_cus = ncu;
-    }
-    return on && conv_variant() != 1 && items >= ncu && d->Cin % 64 == 0 && d->Cin >= 128 && d->Cout % V_COT == 0 &&
+    return on && items >= fen_detail::num_cus() && d->Cin % 64 == 0 && d->Cin >= 128 && d->Cout % V_COT == 0 &&
            d->s2d_in == 0 && d->s2d_out == 0 && !(d->epi & (FEN_EPI_SHUFFLE | FEN_EPI_UNSHUFFLE | FEN_EPI_LAST)) &&
            (size_t)d->B * d->H * d->W * d->Cin * 2 < (size_t)V_BAD && (size_t)9 * d->Cout * d->Cin * 2 < (size_t)V_BAD;
 }
@@ -1566,16 +1497,20 @@ int launch_s(const fen_conv_desc* d, hipStream_t s) {
     const int tpi = ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
     const int coutp = (d->Cout + 15) & ~15;
     dim3 grid(d->B * tpi, coutp / COT);
-    const size_t lds = HALO_BYTES + 3 * COT * 128;   // > 64 KB at COT = 64: opt in once
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_conv3x3_s<T, COT, EPIC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        attr_set = true;
-    }
+    const size_t lds = HALO_BYTES + 3 * COT * 128;   // > 64 KB at COT = 64
+    fen_detail::opt_in_lds<k_conv3x3_s<T, COT, EPIC>>((int)lds);
     hipLaunchKernelGGL((k_conv3x3_s<T, COT, EPIC>), grid, dim3(256), lds, s, *d);
     FEN_CHECK_LAUNCH();
     return FEN_OK;
+}
+
+// the network's epilogue modes get their own kernel instantiation: mode | #residuals << 8 with the
+// residual pointers packed at the front, -1 (the runtime-mode epilogue) otherwise
+int epi_key(const fen_conv_desc* d) {
+    const int nres = d->res[0] ? (d->res[1] ? (d->res[2] ? 3 : 2) : 1) : 0;
+    for (int k = nres; k < 3; ++k)
+        if (d->res[k]) return -1;
+    return d->epi | (nres << 8);
 }
 
 // Kernel selection for one compute dtype T (float, bf16 or f16)
@@ -1583,14 +1518,15 @@ template <typename T>
 int conv_dispatch(const fen_conv_desc* d, hipStream_t s) {
     const int epi = d->epi;
     constexpr bool H16 = sizeof(T) == 2;
+    constexpr int B_ = FEN_EPI_BIAS;
     // the persistent kernels address the input with 32-bit buffer offsets
     const bool small = (size_t)d->B * d->H * d->W * 128 < (size_t)0x7fff0000;
     const bool s2d = d->s2d_in > 0 || d->s2d_out > 0;
-    const bool persist = H16 && d->Cin == 64 && small && !(epi & FEN_EPI_UNSHUFFLE) && conv_variant() != 1 && !s2d;
+    const bool persist = H16 && d->Cin == 64 && small && !(epi & FEN_EPI_UNSHUFFLE) && !s2d;
     if (epi & FEN_EPI_LAST) {
         if (d->Cout > 4 || !d->lr || d->scale <= 0 || d->H % d->scale || d->W % d->scale) return FEN_EINVAL;
         if (epi & ~(FEN_EPI_LAST | FEN_EPI_BIAS)) return FEN_EUNSUPPORTED;
-        if (fen_detail::conv_last_fast_ok(d) && conv_variant() != 1) return fen_detail::launch_conv_last(d, s);
+        if (fen_detail::conv_last_fast_ok(d)) return fen_detail::launch_conv_last(d, s);
         return launch_s<T, 16>(d, s);
     }
     if (!d->y) return FEN_EINVAL;
@@ -1600,13 +1536,12 @@ int conv_dispatch(const fen_conv_desc* d, hipStream_t s) {
             return FEN_EUNSUPPORTED;
     }
     if ((epi & FEN_EPI_UNSHUFFLE) && ((d->H | d->W) & 1)) return FEN_EINVAL;
+    const int key = epi_key(d);
     if (d->y_pool) {
         // the fused 2x2 max pool: bias + ReLU/PReLU stores of the persistent kernels; any other
         // route stores every image of y and pools it in a k_maxpool2 pass
         if constexpr (H16) {
-            constexpr int B_ = FEN_EPI_BIAS;
-            const bool dense = !d->res[0] && !d->res[1] && !d->res[2];
-            if (dense && epi == (B_ | FEN_EPI_PRELU) && d->Cout % 64 == 0 && conv_variant() == 0) {
+            if (key == (B_ | FEN_EPI_PRELU) && d->Cout % 64 == 0) {
                 if (persist) return launch_g<T, B_ | FEN_EPI_PRELU | EPIC_MPOOL>(d, s);
                 if (conv_v_ok(d)) return launch_v<T, B_ | FEN_EPI_PRELU | EPIC_MPOOL>(d, s);
             }
@@ -1618,86 +1553,50 @@ int conv_dispatch(const fen_conv_desc* d, hipStream_t s) {
         if (rc != FEN_OK) return rc;
         return fen_maxpool2(d->dtype, d->B, d->H, d->W, d->Cout, d->y, d->y_pool, s);
     }
-    if (d->Cout % 64 == 0) {
-        if constexpr (H16) {
-            if (persist) {
-                // the network's epilogue modes get their own instantiation (mode | #residuals << 8)
-                const int nres = d->res[0] ? (d->res[1] ? (d->res[2] ? 3 : 2) : 1) : 0;
-                bool dense = true;   // residual pointers packed at the front
-                for (int k = nres; k < 3; ++k) dense = dense && !d->res[k];
-                const int key = dense && conv_variant() != 2 ? (epi | (nres << 8)) : -1;
-                constexpr int B_ = FEN_EPI_BIAS;
-                if (conv_variant() == 3 && key == (B_ | FEN_EPI_PRELU)) return launch_p<T, 64, 4, 1, B_ | FEN_EPI_PRELU>(d, s);
-                if (conv_variant() != 5 && conv_variant() != 3) {
-                    // default: the ping-pong kernel, except where the one-group persistent kernel
-                    // measures faster (pool epilogue 19.2 vs 20.4 us, PReLU-backward 21.8 vs
-                    // 36.3 us at B=32 64x64: the latter's register-heavy epilogue does not fit
-                    // the ping-pong kernel's half-size register budget)
-                    switch (key) {
-                        case B_ | FEN_EPI_PRELU: return launch_g<T, B_ | FEN_EPI_PRELU>(d, s);
-                        case B_ | FEN_EPI_POOL: return launch_p<T, 64, 4, 2, B_ | FEN_EPI_POOL>(d, s);
-                        case B_ | (1 << 8): return launch_g<T, B_ | (1 << 8)>(d, s);
-                        case B_ | FEN_EPI_PRELU | FEN_EPI_SHUFFLE: return launch_g<T, B_ | FEN_EPI_PRELU | FEN_EPI_SHUFFLE>(d, s);
-                        case FEN_EPI_PRELU_BWD: return launch_p<T, 64, 4, 2, FEN_EPI_PRELU_BWD>(d, s);
-                        case FEN_EPI_RELU_BWD: return launch_g<T, FEN_EPI_RELU_BWD>(d, s);
-                        case 0: return launch_g<T, 0>(d, s);
-                        case 1 << 8: return launch_g<T, 1 << 8>(d, s);
-                        case 2 << 8: return launch_g<T, 2 << 8>(d, s);
-                        case 3 << 8: return launch_g<T, 3 << 8>(d, s);
-                        case FEN_EPI_DOT: return launch_g<T, FEN_EPI_DOT>(d, s);
-                        case FEN_EPI_DOT | (1 << 8): return launch_g<T, FEN_EPI_DOT | (1 << 8)>(d, s);
-                        default: break;
-                    }
-                }
-                switch (key) {
-                    case B_ | FEN_EPI_PRELU: return launch_p<T, 64, 4, 2, B_ | FEN_EPI_PRELU>(d, s);
-                    case B_ | FEN_EPI_POOL: return launch_p<T, 64, 4, 2, B_ | FEN_EPI_POOL>(d, s);
-                    case B_ | (1 << 8): return launch_p<T, 64, 4, 2, B_ | (1 << 8)>(d, s);
-                    case B_ | FEN_EPI_PRELU | FEN_EPI_SHUFFLE:
-                        return launch_p<T, 64, 4, 2, B_ | FEN_EPI_PRELU | FEN_EPI_SHUFFLE>(d, s);
-                    case FEN_EPI_PRELU_BWD: return launch_p<T, 64, 4, 2, FEN_EPI_PRELU_BWD>(d, s);
-                    case 0: return launch_p<T, 64, 4, 2, 0>(d, s);
-                    case 1 << 8: return launch_p<T, 64, 4, 2, 1 << 8>(d, s);
-                    case 2 << 8: return launch_p<T, 64, 4, 2, 2 << 8>(d, s);
-                    case 3 << 8: return launch_p<T, 64, 4, 2, 3 << 8>(d, s);
-                    default: return launch_p<T, 64, 4, 2, -1>(d, s);
-                }
-            }
-        }
-        if constexpr (H16) {
-            if (conv_v_ok(d)) {
-                const int nres = d->res[0] ? (d->res[1] ? (d->res[2] ? 3 : 2) : 1) : 0;
-                bool dense = true;
-                for (int k = nres; k < 3; ++k) dense = dense && !d->res[k];
-                constexpr int B_ = FEN_EPI_BIAS;
-                switch (dense ? (epi | (nres << 8)) : -1) {
-                    case B_ | FEN_EPI_PRELU: return launch_v<T, B_ | FEN_EPI_PRELU>(d, s);
-                    case B_: return launch_v<T, B_>(d, s);
-                    case FEN_EPI_PRELU_BWD: return launch_v<T, FEN_EPI_PRELU_BWD>(d, s);
-                    case FEN_EPI_RELU_BWD: return launch_v<T, FEN_EPI_RELU_BWD>(d, s);
-                    case 0: return launch_v<T, 0>(d, s);
-                    default: break;   // (the runtime-mode epilogue spills at this wave shape: streamed kernel)
-                }
-            }
-        }
-        if constexpr (H16) {
-            // the upsampler dgrads (Cin = 4C): their epilogue modes as compile-time constants (no
-            // residual loads or other modes' code in the epilogue's register budget)
-#ifndef CONV_S_GENERIC   // A/B only: every streamed conv on the runtime-mode epilogue
-            if (!d->res[0] && !d->res[1] && !d->res[2] && !s2d) {
-                if (epi == (FEN_EPI_PRELU_BWD | FEN_EPI_UNSHUFFLE))
-                    return launch_s<T, 64, FEN_EPI_PRELU_BWD | FEN_EPI_UNSHUFFLE>(d, s);
-                if (epi == 0) return launch_s<T, 64, 0>(d, s);
-            }
-#endif
-        }
-        return launch_s<T, 64>(d, s);
-    }
     // (Cout 16 from Cin 64 -- VGG conv1_1's data gradient -- on the one-group persistent kernel
     // with a 16-row resident filter measured 149 us vs the streamed kernel's 123 at B = 32, 256^2:
     // its per-tile residual loads and halo wait are exposed; r6)
-    if (d->Cout % 16 == 0) return launch_s<T, 16>(d, s);
-    return FEN_EUNSUPPORTED;
+    if (d->Cout % 64) return d->Cout % 16 == 0 ? launch_s<T, 16>(d, s) : FEN_EUNSUPPORTED;
+    if constexpr (H16) {
+        if (persist) {
+            // the ping-pong kernel, except where the one-group persistent kernel measures faster
+            // (pool epilogue 19.2 vs 20.4 us, PReLU-backward 21.8 vs 36.3 us at B=32 64x64: the
+            // latter's register-heavy epilogue does not fit the ping-pong kernel's half-size
+            // register budget) and for the modes without an instantiation of their own
+            switch (key) {
+                case B_ | FEN_EPI_PRELU: return launch_g<T, B_ | FEN_EPI_PRELU>(d, s);
+                case B_ | FEN_EPI_POOL: return launch_p<T, 64, 4, 2, B_ | FEN_EPI_POOL>(d, s);
+                case B_ | (1 << 8): return launch_g<T, B_ | (1 << 8)>(d, s);
+                case B_ | FEN_EPI_PRELU | FEN_EPI_SHUFFLE: return launch_g<T, B_ | FEN_EPI_PRELU | FEN_EPI_SHUFFLE>(d, s);
+                case FEN_EPI_PRELU_BWD: return launch_p<T, 64, 4, 2, FEN_EPI_PRELU_BWD>(d, s);
+                case FEN_EPI_RELU_BWD: return launch_g<T, FEN_EPI_RELU_BWD>(d, s);
+                case 0: return launch_g<T, 0>(d, s);
+                case 1 << 8: return launch_g<T, 1 << 8>(d, s);
+                case 2 << 8: return launch_g<T, 2 << 8>(d, s);
+                case 3 << 8: return launch_g<T, 3 << 8>(d, s);
+                case FEN_EPI_DOT: return launch_g<T, FEN_EPI_DOT>(d, s);
+                case FEN_EPI_DOT | (1 << 8): return launch_g<T, FEN_EPI_DOT | (1 << 8)>(d, s);
+                default: return launch_p<T, 64, 4, 2, -1>(d, s);
+            }
+        }
+        if (conv_v_ok(d)) {
+            if (key == (B_ | FEN_EPI_PRELU)) return launch_v<T, B_ | FEN_EPI_PRELU>(d, s);
+            if (key == B_) return launch_v<T, B_>(d, s);
+            if (key == FEN_EPI_PRELU_BWD) return launch_v<T, FEN_EPI_PRELU_BWD>(d, s);
+            if (key == FEN_EPI_RELU_BWD) return launch_v<T, FEN_EPI_RELU_BWD>(d, s);
+            if (key == 0) return launch_v<T, 0>(d, s);
+            // (the runtime-mode epilogue spills at this wave shape: streamed kernel)
+        }
+        // the upsampler dgrads (Cin = 4C): their epilogue modes as compile-time constants (no
+        // residual loads or other modes' code in the epilogue's register budget)
+#ifndef CONV_S_GENERIC   // A/B only: every streamed conv on the runtime-mode epilogue
+        if (!s2d) {
+            if (key == (FEN_EPI_PRELU_BWD | FEN_EPI_UNSHUFFLE)) return launch_s<T, 64, FEN_EPI_PRELU_BWD | FEN_EPI_UNSHUFFLE>(d, s);
+            if (key == 0) return launch_s<T, 64, 0>(d, s);
+        }
+#endif
+    }
+    return launch_s<T, 64>(d, s);
 }
 
 }  // namespace
@@ -1705,7 +1604,7 @@ int conv_dispatch(const fen_conv_desc* d, hipStream_t s) {
 extern "C" int fen_conv3x3(const fen_conv_desc* d, void* stream) {
     if (!d || !d->x || !d->w || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0)
         return FEN_EINVAL;
-    if (d->dtype != FEN_F32 && d->dtype != FEN_BF16 && d->dtype != FEN_F16) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(d->dtype)) return st;
     // 16-B channel chunks: Cin % 8 (16-bit) / % 4 (f32); Cin == 64 takes the persistent kernels
     if ((d->Cin * (d->dtype == FEN_F32 ? 4 : 2)) % 16) return FEN_EUNSUPPORTED;
     const int epi = d->epi;
@@ -1735,10 +1634,5 @@ extern "C" int fen_conv3x3(const fen_conv_desc* d, void* stream) {
         return FEN_EUNSUPPORTED;
     if ((epi & (FEN_EPI_SHUFFLE | FEN_EPI_UNSHUFFLE)) == (FEN_EPI_SHUFFLE | FEN_EPI_UNSHUFFLE))
         return FEN_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->dtype) {
-        case FEN_BF16: return conv_dispatch<bf16>(d, s);
-        case FEN_F16: return conv_dispatch<f16>(d, s);
-        default: return conv_dispatch<float>(d, s);
-    }
+    return fen_detail::with_dtype(d->dtype, [&](auto tag) { return conv_dispatch<decltype(tag)>(d, (hipStream_t)stream); });
 }

@@ -270,8 +270,6 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
     }
 }
 
-int g_cus = 0;
-
 }  // namespace
 
 namespace fen_detail {
@@ -283,31 +281,20 @@ bool conv_last_fast_ok(const fen_conv_desc* d) {
 }
 
 int launch_conv_last(const fen_conv_desc* d, hipStream_t s) {
-    if (g_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_cus <= 0) g_cus = 256;
-    }
     const int ntiles = d->B * (d->H >> 4) * (d->W >> 4);
-    const int grid = ntiles < g_cus ? ntiles : g_cus;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_conv_last<bf16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CL_LDS);
-        (void)hipFuncSetAttribute((const void*)k_conv_last<bf16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CL_LDS);
-        (void)hipFuncSetAttribute((const void*)k_conv_last<f16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CL_LDS);
-        (void)hipFuncSetAttribute((const void*)k_conv_last<f16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CL_LDS);
-        attr_set = true;
-    }
-    if (d->dtype == FEN_F16) {
-        if (d->hr) hipLaunchKernelGGL((k_conv_last<f16, true>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
-        else hipLaunchKernelGGL((k_conv_last<f16, false>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
-    } else {
-        if (d->hr) hipLaunchKernelGGL((k_conv_last<bf16, true>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
-        else hipLaunchKernelGGL((k_conv_last<bf16, false>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    const int grid = persistent_grid(ntiles, 1);
+    return with_dtype16(d->dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if (d->hr) {
+            opt_in_lds<k_conv_last<T, true>>(CL_LDS);
+            hipLaunchKernelGGL((k_conv_last<T, true>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
+        } else {
+            opt_in_lds<k_conv_last<T, false>>(CL_LDS);
+            hipLaunchKernelGGL((k_conv_last<T, false>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
+        }
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 }  // namespace fen_detail

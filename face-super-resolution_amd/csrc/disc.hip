@@ -399,6 +399,15 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_g(size_t npx, int C, const
         *(uint4*)(dy + p * C + g * V) = pack16<T>(dv);
     }
 }
+
+// the discriminator's kernels are bf16 / f32: the fp16 code is FEN_EINVAL like any other
+template <typename F>
+int with_dtype_no_f16(int dtype, F&& f) {
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        if constexpr (std::is_same<decltype(tag), f16>::value) return FEN_EINVAL;
+        else return f(tag);
+    });
+}
 }  // namespace
 
 #define STREAM ((hipStream_t)stream)
@@ -413,25 +422,17 @@ extern "C" int fen_bn_stats_n(int dtype, int ng, size_t npx, int C, const void* 
     if (!y || !stat || !work || npx == 0 || ng < 1 || ng > 65535 || C % 8 || C > 2048 ||
         (rmean != nullptr) != (rvar != nullptr))
         return FEN_EINVAL;
-    if (dtype == FEN_BF16) {
-        hipLaunchKernelGGL(k_bn_stats<bf16>, dim3(BN_BLOCKS, ng), dim3(256), 0, STREAM, npx, C, (const bf16*)y, work);
+    return with_dtype_no_f16(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_bn_stats<T>, dim3(BN_BLOCKS, ng), dim3(256), 0, STREAM, npx, C, (const T*)y, work);
         FEN_CHECK_LAUNCH();
         for (int gi = 0; gi < ng; ++gi)                      // in group order: the running statistics
-            hipLaunchKernelGGL(k_bn_finalize<bf16>, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, STREAM, BN_BLOCKS, npx, C,
-                               (const bf16*)y + (size_t)gi * npx * C, work + (size_t)gi * BN_BLOCKS * 2 * C, eps, momentum,
+            hipLaunchKernelGGL(k_bn_finalize<T>, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, STREAM, BN_BLOCKS, npx, C,
+                               (const T*)y + (size_t)gi * npx * C, work + (size_t)gi * BN_BLOCKS * 2 * C, eps, momentum,
                                stat + (size_t)gi * 2 * C, rmean, rvar);
-    } else if (dtype == FEN_F32) {
-        hipLaunchKernelGGL(k_bn_stats<float>, dim3(BN_BLOCKS, ng), dim3(256), 0, STREAM, npx, C, (const float*)y, work);
         FEN_CHECK_LAUNCH();
-        for (int gi = 0; gi < ng; ++gi)
-            hipLaunchKernelGGL(k_bn_finalize<float>, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, STREAM, BN_BLOCKS, npx, C,
-                               (const float*)y + (size_t)gi * npx * C, work + (size_t)gi * BN_BLOCKS * 2 * C, eps, momentum,
-                               stat + (size_t)gi * 2 * C, rmean, rvar);
-    } else {
-        return FEN_EINVAL;
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+        return FEN_OK;
+    });
 }
 
 // one group: stat [2C], work fen_bn_work_floats(C)
@@ -449,37 +450,27 @@ extern "C" int fen_bn_apply_n(int dtype, int ng, size_t npx, int C, const void* 
     if (!y || !mean || !rstd || !gamma || !beta || !out || C % 8 || ng < 1 || ng > 65535 || (ng > 1 && mstride < C))
         return FEN_EINVAL;
     if (C > 1024) return FEN_EUNSUPPORTED;
-    if (dtype != FEN_BF16 && dtype != FEN_F32) return FEN_EINVAL;
-    const int G = C / (dtype == FEN_F32 ? 4 : 8);
-    if (G <= 256 && 256 % G == 0) {
-        const size_t per = (size_t)(256 / G) * BN_PPT;
-        const unsigned nb = (unsigned)((npx + per - 1) / per);
-        if (dtype == FEN_BF16)
-            hipLaunchKernelGGL(k_bn_apply_g<bf16>, dim3(nb, ng), dim3(256), 0, STREAM, npx, C, (const bf16*)y, mean, rstd,
-                               gamma, beta, slope, (bf16*)out, mstride);
-        else
-            hipLaunchKernelGGL(k_bn_apply_g<float>, dim3(nb, ng), dim3(256), 0, STREAM, npx, C, (const float*)y, mean,
-                               rstd, gamma, beta, slope, (float*)out, mstride);
-        FEN_CHECK_LAUNCH();
-        return FEN_OK;
-    }
-    const size_t esz = dtype == FEN_F32 ? 4 : 2;
-    for (int gi = 0; gi < ng; ++gi) {                        // other channel counts: a launch per group
-        const char* yg = (const char*)y + (size_t)gi * npx * C * esz;
-        char* og = (char*)out + (size_t)gi * npx * C * esz;
-        const float *mg = mean + (size_t)gi * mstride, *rg = rstd + (size_t)gi * mstride;
-        if (dtype == FEN_BF16) {
-            const size_t nv = npx * C / 8;
-            hipLaunchKernelGGL(k_bn_apply<bf16>, dim3(nblk(nv, 256 * BN_NPT)), dim3(256), 0, STREAM, nv, C, (const bf16*)yg,
-                               mg, rg, gamma, beta, slope, (bf16*)og);
-        } else {
-            const size_t nv = npx * C / 4;
-            hipLaunchKernelGGL(k_bn_apply<float>, dim3(nblk(nv, 256 * BN_NPT)), dim3(256), 0, STREAM, nv, C,
-                               (const float*)yg, mg, rg, gamma, beta, slope, (float*)og);
+    return with_dtype_no_f16(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        constexpr int V = Tr<T>::EPC;
+        const int G = C / V;
+        if (G <= 256 && 256 % G == 0) {
+            const size_t per = (size_t)(256 / G) * BN_PPT;
+            const unsigned nb = (unsigned)((npx + per - 1) / per);
+            hipLaunchKernelGGL(k_bn_apply_g<T>, dim3(nb, ng), dim3(256), 0, STREAM, npx, C, (const T*)y, mean, rstd, gamma,
+                               beta, slope, (T*)out, mstride);
+            FEN_CHECK_LAUNCH();
+            return FEN_OK;
         }
-        FEN_CHECK_LAUNCH();
-    }
-    return FEN_OK;
+        const size_t nv = npx * C / V;
+        for (int gi = 0; gi < ng; ++gi) {                    // other channel counts: a launch per group
+            const size_t o = (size_t)gi * npx * C;
+            hipLaunchKernelGGL(k_bn_apply<T>, dim3(nblk(nv, 256 * BN_NPT)), dim3(256), 0, STREAM, nv, C, (const T*)y + o,
+                               mean + (size_t)gi * mstride, rstd + (size_t)gi * mstride, gamma, beta, slope, (T*)out + o);
+            FEN_CHECK_LAUNCH();
+        }
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_bn_apply(int dtype, size_t npx, int C, const void* y, const float* mean, const float* rstd,
@@ -496,52 +487,37 @@ extern "C" int fen_bn_bwd_n(int dtype, int ng, size_t npx, int C, const void* da
                             int accumulate, float* work, void* stream) {
     if (!da || !y || !stat || !gamma || !beta || !dy || !work || C % 8 || C > 2048 || ng < 1 || ng > 65535)
         return FEN_EINVAL;
-    if (dtype != FEN_BF16 && dtype != FEN_F32) return FEN_EINVAL;
-    float* red2 = work + (size_t)ng * BN_BLOCKS * 2 * C;
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_bn_bwd_reduce<bf16>, dim3(BN_BLOCKS, ng), dim3(256), 0, STREAM, npx, C, (const bf16*)da,
-                           (const bf16*)y, stat, gamma, beta, slope, work);
-    else
-        hipLaunchKernelGGL(k_bn_bwd_reduce<float>, dim3(BN_BLOCKS, ng), dim3(256), 0, STREAM, npx, C, (const float*)da,
-                           (const float*)y, stat, gamma, beta, slope, work);
-    FEN_CHECK_LAUNCH();
-    for (int gi = 0; gi < ng; ++gi)                          // in group order: dgamma / dbeta accumulate
-        hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, STREAM, BN_BLOCKS, C,
-                           work + (size_t)gi * BN_BLOCKS * 2 * C, dgamma, dbeta, red2 + (size_t)gi * 2 * C,
-                           gi ? 1 : accumulate);
-    FEN_CHECK_LAUNCH();
-    const int G = C / (dtype == FEN_F32 ? 4 : 8);
-    if (G <= 256 && 256 % G == 0) {
-        const size_t per = (size_t)(256 / G) * BN_PPT;
-        const unsigned nb = (unsigned)((npx + per - 1) / per);
-        if (dtype == FEN_BF16)
-            hipLaunchKernelGGL(k_bn_bwd_apply_g<bf16>, dim3(nb, ng), dim3(256), 0, STREAM, npx, C, (const bf16*)da,
-                               (const bf16*)y, stat, gamma, beta, slope, red2, (bf16*)dy);
-        else
-            hipLaunchKernelGGL(k_bn_bwd_apply_g<float>, dim3(nb, ng), dim3(256), 0, STREAM, npx, C, (const float*)da,
-                               (const float*)y, stat, gamma, beta, slope, red2, (float*)dy);
+    return with_dtype_no_f16(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        float* red2 = work + (size_t)ng * BN_BLOCKS * 2 * C;
+        hipLaunchKernelGGL(k_bn_bwd_reduce<T>, dim3(BN_BLOCKS, ng), dim3(256), 0, STREAM, npx, C, (const T*)da,
+                           (const T*)y, stat, gamma, beta, slope, work);
         FEN_CHECK_LAUNCH();
-        return FEN_OK;
-    }
-    const size_t esz = dtype == FEN_F32 ? 4 : 2;
-    for (int gi = 0; gi < ng; ++gi) {                        // other channel counts: a launch per group
-        const size_t o = (size_t)gi * npx * C * esz;
-        const float* sg = stat + (size_t)gi * 2 * C;
-        const float* rg = red2 + (size_t)gi * 2 * C;
-        if (dtype == FEN_BF16) {
-            const size_t nv = npx * C / 8;
-            hipLaunchKernelGGL(k_bn_bwd_apply<bf16>, dim3(nblk(nv)), dim3(256), 0, STREAM, nv, npx, C,
-                               (const bf16*)((const char*)da + o), (const bf16*)((const char*)y + o), sg, gamma, beta, slope,
-                               rg, (bf16*)((char*)dy + o));
-        } else {
-            const size_t nv = npx * C / 4;
-            hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(nblk(nv)), dim3(256), 0, STREAM, nv, npx, C,
-                               (const float*)((const char*)da + o), (const float*)((const char*)y + o), sg, gamma, beta,
-                               slope, rg, (float*)((char*)dy + o));
+        for (int gi = 0; gi < ng; ++gi)                      // in group order: dgamma / dbeta accumulate
+            hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64 * FIN_WAVES), 0, STREAM, BN_BLOCKS, C,
+                               work + (size_t)gi * BN_BLOCKS * 2 * C, dgamma, dbeta, red2 + (size_t)gi * 2 * C,
+                               gi ? 1 : accumulate);
+        FEN_CHECK_LAUNCH();
+        constexpr int V = Tr<T>::EPC;
+        const int G = C / V;
+        if (G <= 256 && 256 % G == 0) {
+            const size_t per = (size_t)(256 / G) * BN_PPT;
+            const unsigned nb = (unsigned)((npx + per - 1) / per);
+            hipLaunchKernelGGL(k_bn_bwd_apply_g<T>, dim3(nb, ng), dim3(256), 0, STREAM, npx, C, (const T*)da, (const T*)y,
+                               stat, gamma, beta, slope, red2, (T*)dy);
+            FEN_CHECK_LAUNCH();
+            return FEN_OK;
         }
-        FEN_CHECK_LAUNCH();
-    }
-    return FEN_OK;
+        const size_t nv = npx * C / V;
+        for (int gi = 0; gi < ng; ++gi) {                    // other channel counts: a launch per group
+            const size_t o = (size_t)gi * npx * C;
+            hipLaunchKernelGGL(k_bn_bwd_apply<T>, dim3(nblk(nv)), dim3(256), 0, STREAM, nv, npx, C, (const T*)da + o,
+                               (const T*)y + o, stat + (size_t)gi * 2 * C, gamma, beta, slope, red2 + (size_t)gi * 2 * C,
+                               (T*)dy + o);
+            FEN_CHECK_LAUNCH();
+        }
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_bn_bwd(int dtype, size_t npx, int C, const void* da, const void* y, const float* stat,
@@ -552,62 +528,40 @@ extern "C" int fen_bn_bwd(int dtype, size_t npx, int C, const void* da, const vo
 
 extern "C" int fen_subsample2(int dtype, int B, int H, int W, int C, const void* x, void* y, void* stream) {
     if (!x || !y || (H | W) & 1 || C % 8) return FEN_EINVAL;
-    if (dtype == FEN_BF16) {
-        const size_t n = (size_t)B * (H / 2) * (W / 2) * (C / 8);
-        hipLaunchKernelGGL(k_subsample2<bf16>, dim3(nblk(n)), dim3(256), 0, STREAM, B, H / 2, W / 2, C, (const bf16*)x,
-                           (bf16*)y);
-    } else if (dtype == FEN_F32) {
-        const size_t n = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-        hipLaunchKernelGGL(k_subsample2<float>, dim3(nblk(n)), dim3(256), 0, STREAM, B, H / 2, W / 2, C,
-                           (const float*)x, (float*)y);
-    } else {
-        return FEN_EINVAL;
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return with_dtype_no_f16(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const size_t n = (size_t)B * (H / 2) * (W / 2) * (C / Tr<T>::EPC);
+        hipLaunchKernelGGL(k_subsample2<T>, dim3(nblk(n)), dim3(256), 0, STREAM, B, H / 2, W / 2, C, (const T*)x, (T*)y);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_zero_insert2(int dtype, int B, int Ho, int Wo, int C, const void* dy, void* out, void* stream) {
     if (!dy || !out || C % 8) return FEN_EINVAL;
-    if (dtype == FEN_BF16) {
-        const size_t n = (size_t)B * 2 * Ho * 2 * Wo * (C / 8);
-        hipLaunchKernelGGL(k_zero_insert2<bf16>, dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const bf16*)dy,
-                           (bf16*)out);
-    } else if (dtype == FEN_F32) {
-        const size_t n = (size_t)B * 2 * Ho * 2 * Wo * (C / 4);
-        hipLaunchKernelGGL(k_zero_insert2<float>, dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C,
-                           (const float*)dy, (float*)out);
-    } else {
-        return FEN_EINVAL;
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return with_dtype_no_f16(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const size_t n = (size_t)B * 2 * Ho * 2 * Wo * (C / Tr<T>::EPC);
+        hipLaunchKernelGGL(k_zero_insert2<T>, dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const T*)dy, (T*)out);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_s2d2(int dtype, int B, int H, int W, int C, const void* x, void* y, int inverse, void* stream) {
     if (!x || !y || B <= 0 || H <= 0 || W <= 0 || (H | W) & 1 || C % 8) return FEN_EINVAL;
-    const int V = dtype == FEN_F32 ? 4 : 8;
-    const size_t n = (size_t)B * H * W * C / V;
     const int Ho = H / 2, Wo = W / 2;
-    if (dtype == FEN_BF16 || dtype == FEN_F16) {
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        // (a pure permutation of 16-B vectors: fp16 moves through the bf16 kernel)
+        using T = std::conditional_t<sizeof(tag) == 2, bf16, float>;
+        const size_t n = (size_t)B * H * W * C / Tr<T>::EPC;
         if (inverse)
-            hipLaunchKernelGGL((k_s2d2<bf16, true>), dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const bf16*)x,
-                               (bf16*)y);
+            hipLaunchKernelGGL((k_s2d2<T, true>), dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const T*)x, (T*)y);
         else
-            hipLaunchKernelGGL((k_s2d2<bf16, false>), dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const bf16*)x,
-                               (bf16*)y);
-    } else if (dtype == FEN_F32) {
-        if (inverse)
-            hipLaunchKernelGGL((k_s2d2<float, true>), dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const float*)x,
-                               (float*)y);
-        else
-            hipLaunchKernelGGL((k_s2d2<float, false>), dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C,
-                               (const float*)x, (float*)y);
-    } else {
-        return FEN_EINVAL;
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+            hipLaunchKernelGGL((k_s2d2<T, false>), dim3(nblk(n)), dim3(256), 0, STREAM, B, Ho, Wo, C, (const T*)x, (T*)y);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 // The phase-major filter of a space-to-depth stride-2 conv (see fen_s2d2), fp32 OIHW:

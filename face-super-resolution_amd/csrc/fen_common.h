@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "fen.h"
 
@@ -324,8 +325,62 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 // kept for fen_last_hip_error().
 namespace fen_detail {
 extern thread_local int last_hip_error;
+
+// The one dtype dispatch of the C-ABI: f(bf16{}), f(f16{}) or f(float{}), whose status it returns;
+// any other code is FEN_EINVAL and f -- and with it every launch -- is never reached.  f casts
+// its arguments through `using T = decltype(tag)`; a 16-bit-only entry point answers the float
+// tag with `if constexpr (sizeof(T) == 2)` so that no float kernel is instantiated for it.
+template <typename F>
+int with_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case FEN_BF16: return f(bf16{});
+        case FEN_F16: return f(f16{});
+        case FEN_F32: return f(float{});
+        default: return FEN_EINVAL;
+    }
 }
-#define FEN_CHECK_LAUNCH()                                        \
+// The same for an entry point with 16-bit kernels only: float is FEN_EUNSUPPORTED, and f is
+// instantiated for bf16 and f16 alone.
+template <typename F>
+int with_dtype16(int dtype, F&& f) {
+    return with_dtype(dtype, [&](auto tag) -> int {
+        if constexpr (sizeof(tag) == 2) return f(tag);
+        return FEN_EUNSUPPORTED;
+    });
+}
+// FEN_EINVAL for a code that is no dtype: ahead of a *_supported() test, which answers a wrong
+// code and an unsupported dtype alike with 0
+inline int check_dtype(int dtype) {
+    return with_dtype(dtype, [](auto) -> int { return FEN_OK; });
+}
+
+// Launch geometry (defined in small.hip).  Both caches are per device, indexed by the calling
+// thread's current device, so a process that drives several devices gets each one's own CU
+// count and opt-in; a process on one device makes one query and one opt-in per kernel.
+constexpr int MAX_DEVICES = 64;   // (as fen_status_word's table; an id past it shares slot 0)
+int device_slot();                // current device id, 0 when the query fails
+int num_cus();                    // its multiprocessor count, 256 when the query fails
+// Grid of a persistent kernel: one block per CU, rounded down to whole sets of the ncot blocks
+// that share a tile (never below `floor`), and no more than the ntiles * ncot work items.
+inline int persistent_grid(int ntiles, int ncot, int floor = 0) {
+    int grid = num_cus();
+    grid -= grid % ncot;
+    if (grid < floor) grid = floor;
+    const int maxg = ntiles * ncot;
+    return grid < maxg ? grid : maxg;
+}
+// A kernel with more than 64 KB of dynamic LDS opts in once per (kernel, device).
+template <auto Kernel>
+void opt_in_lds(int bytes) {
+    static bool done[MAX_DEVICES] = {};
+    bool& d = done[device_slot()];
+    if (!d) {
+        (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        d = true;
+    }
+}
+}  // namespace fen_detail
+#define FEN_CHECK_LAUNCH()                                      \
     do {                                                          \
         hipError_t e_ = hipGetLastError();                        \
         if (e_ != hipSuccess && e_ != hipErrorNotReady) {         \

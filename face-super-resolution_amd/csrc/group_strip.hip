@@ -885,25 +885,9 @@ __global__ __launch_bounds__(512, 1) void k_group_strip(const GsArgs A) {
 #endif
 }
 
-int g_gs_cus = 0;
-int gs_num_cus() {
-    if (g_gs_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_gs_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_gs_cus <= 0) g_gs_cus = 256;
-    }
-    return g_gs_cus;
-}
-
 template <typename T, bool SAVE, bool MULTI = false>
 void launch_gs(const GsArgs& a, int grid, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_group_strip<T, SAVE, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  GS_LDS);
-        attr = true;
-    }
+    fen_detail::opt_in_lds<k_group_strip<T, SAVE, MULTI>>(GS_LDS);
     hipLaunchKernelGGL((k_group_strip<T, SAVE, MULTI>), dim3(grid), dim3(512), GS_LDS, s, a);
 }
 
@@ -928,6 +912,7 @@ __global__ __launch_bounds__(256) void k_tab_write(unsigned int* __restrict__ ds
 int chain_tab(const fen_group_strip_desc* d, int ng, const fen_group_strip_chain_tail* tail, std::vector<GsTab>& tab) {
     if (!d || ng <= 0) return FEN_EINVAL;
     const fen_group_strip_desc& d0 = d[0];
+    if (const int st = fen_detail::check_dtype(d0.dtype)) return st;
     if (!fen_group_strip_supported(d0.dtype, d0.B, d0.H, d0.W, d0.C, d0.Cr, d0.nb)) return FEN_EUNSUPPORTED;
     const int rows = ng + (tail ? 1 : 0);
     if (rows * (d0.nb + 1) > 254) return FEN_EUNSUPPORTED;                    // step tags
@@ -990,6 +975,7 @@ extern "C" size_t fen_group_strip_work_bytes(int B, int H) { return ws_layout(B,
 
 extern "C" int fen_group_strip(const fen_group_strip_desc* d, void* stream) {
     if (!d || !d->x || !d->y || !d->work) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(d->dtype)) return st;
     if (!fen_group_strip_supported(d->dtype, d->B, d->H, d->W, d->C, d->Cr, d->nb)) return FEN_EUNSUPPORTED;
     if (d->work_bytes < fen_group_strip_work_bytes(d->B, d->H)) return FEN_EINVAL;
     GsArgs a{};
@@ -1019,17 +1005,13 @@ extern "C" int fen_group_strip(const fen_group_strip_desc* d, void* stream) {
     if (!d->wg || !d->bg) return FEN_EINVAL;
     a.w[2 * d->nb] = d->wg, a.bias[2 * d->nb] = d->bg;
     const int grid = d->B * (d->H / SR);
-    (void)gs_num_cus();
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == FEN_F16) {
-        if (a.save) launch_gs<f16, true>(a, grid, s);
-        else launch_gs<f16, false>(a, grid, s);
-    } else {
-        if (a.save) launch_gs<bf16, true>(a, grid, s);
-        else launch_gs<bf16, false>(a, grid, s);
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype16(d->dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if (a.save) launch_gs<T, true>(a, grid, (hipStream_t)stream);
+        else launch_gs<T, false>(a, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" size_t fen_group_strip_chain_work_bytes(int B, int H, int ng) {
@@ -1077,14 +1059,11 @@ extern "C" int fen_group_strip_chain(const fen_group_strip_desc* d, int ng, cons
     a.save = d0.save ? 1 : 0;
     a.pre_elide = d0.pre_elide;
     const int grid = d0.B * (d0.H / SR);
-    hipStream_t s = (hipStream_t)stream;
-    if (d0.dtype == FEN_F16) {
-        if (a.save) launch_gs<f16, true, true>(a, grid, s);
-        else launch_gs<f16, false, true>(a, grid, s);
-    } else {
-        if (a.save) launch_gs<bf16, true, true>(a, grid, s);
-        else launch_gs<bf16, false, true>(a, grid, s);
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype16(d0.dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if (a.save) launch_gs<T, true, true>(a, grid, (hipStream_t)stream);
+        else launch_gs<T, false, true>(a, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }

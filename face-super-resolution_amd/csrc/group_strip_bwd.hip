@@ -688,11 +688,7 @@ __global__ __launch_bounds__(512, 1) void k_group_strip_bwd(const GsbArgs A) {
 
 template <typename T>
 void launch_gsb(const GsbArgs& a, int grid, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_group_strip_bwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, GSB_LDS);
-        attr = true;
-    }
+    fen_detail::opt_in_lds<k_group_strip_bwd<T>>(GSB_LDS);
     hipLaunchKernelGGL(k_group_strip_bwd<T>, dim3(grid), dim3(512), GSB_LDS, s, a);
 }
 
@@ -710,6 +706,7 @@ extern "C" int fen_group_strip_bwd_supported(int dtype, int B, int H, int W, int
 
 extern "C" int fen_group_strip_bwd(const fen_group_strip_bwd_desc* d, void* stream) {
     if (!d || !d->dy || !d->dx || !d->work || !d->wgt) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(d->dtype)) return st;
     if (!fen_group_strip_bwd_supported(d->dtype, d->B, d->H, d->W, d->C, d->Cr, d->nb)) return FEN_EUNSUPPORTED;
     if (d->work_bytes < fen_group_strip_bwd_work_bytes(d->B, d->H)) return FEN_EINVAL;
     if (d->dx == d->dy || (d->dres && d->dres == d->dx)) return FEN_EINVAL;
@@ -734,9 +731,9 @@ extern "C" int fen_group_strip_bwd(const fen_group_strip_bwd_desc* d, void* stre
         a.dw1p[j] = d->dw1p[j], a.dw2p[j] = d->dw2p[j];
     }
     const int grid = d->B * (d->H / SR);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == FEN_F16) launch_gsb<f16>(a, grid, s);
-    else launch_gsb<bf16>(a, grid, s);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype16(d->dtype, [&](auto tag) -> int {
+        launch_gsb<decltype(tag)>(a, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }

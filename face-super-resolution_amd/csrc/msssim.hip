@@ -324,6 +324,7 @@ extern "C" int fen_msssim(int dtype, int B, int C, int H, int W, const float* pr
     if (!pred || !target || !window1d || !weights_dev || !work || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0)
         return FEN_EINVAL;
     if (grad_mode < 0 || grad_mode > 2 || (grad_mode && !grad)) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(dtype)) return st;
     if (grad_mode == 2 && (C > 3 || (dtype != FEN_F32 && dtype != FEN_BF16))) return FEN_EINVAL;
     if (window_size != 2 * SR + 1) return FEN_EUNSUPPORTED;
     if (levels < 1 || levels > ML) return FEN_EUNSUPPORTED;

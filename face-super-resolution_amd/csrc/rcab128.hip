@@ -506,16 +506,9 @@ __global__ __launch_bounds__(512, 1) void k_rcab128(const K128 A) {
     }
 }
 
-int g_c128_cus = 0;
-
 template <typename T, int MODE, bool COMB>
 void launch128(const K128& a, int grid, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_rcab128<T, MODE, COMB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS128);
-        attr = true;
-    }
+    fen_detail::opt_in_lds<k_rcab128<T, MODE, COMB>>(LDS128);
     hipLaunchKernelGGL((k_rcab128<T, MODE, COMB>), dim3(grid), dim3(512), LDS128, s, a);
 }
 
@@ -541,6 +534,7 @@ extern "C" int fen_rcab_c128_tiles(int H, int W) { return (H / TR) * (W / TW); }
 
 extern "C" int fen_rcab_c128(const fen_rcab_c128_desc* d, void* stream) {
     if (!d || !d->x || !d->w || !d->bias || !d->y) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(d->dtype)) return st;
     if (!fen_rcab_c128_supported(d->dtype, d->B, d->H, d->W, d->C, d->Cr > 0 ? d->Cr : 1)) return FEN_EUNSUPPORTED;
     const int mode = d->mode;
     if (mode < 1 || mode > 4) return FEN_EINVAL;
@@ -557,17 +551,10 @@ extern "C" int fen_rcab_c128(const fen_rcab_c128_desc* d, void* stream) {
     a.x = d->x, a.tp = d->tp, a.pp = d->pp, a.pfc1 = d->pfc1, a.pfc2 = d->pfc2, a.ps = d->ps;
     a.xo = comb ? d->xo : nullptr;
     a.w = d->w, a.bias = d->bias, a.alpha = d->alpha, a.res = d->res, a.y = d->y, a.z1 = d->z1, a.part = d->part;
-    if (g_c128_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_c128_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_c128_cus <= 0) g_c128_cus = 256;
-    }
-    const int ntiles = d->B * (d->H / TR) * (d->W / TW);
-    const int grid = ntiles < g_c128_cus ? ntiles : g_c128_cus;
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == FEN_F16) dispatch128<f16>(a, mode, comb, grid, s);
-    else dispatch128<bf16>(a, mode, comb, grid, s);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    const int grid = fen_detail::persistent_grid(d->B * (d->H / TR) * (d->W / TW), 1);
+    return fen_detail::with_dtype16(d->dtype, [&](auto tag) -> int {
+        dispatch128<decltype(tag)>(a, mode, comb, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }

@@ -1035,16 +1035,9 @@ __global__ __launch_bounds__(512, 1) void k_rcab_d(const RdArgs A) {
 #endif
 }
 
-int g_cus = 0;
-
 template <typename T, bool DEFER, bool TRAIN, bool BWD = false, bool GC = false, bool SEB = false>
 void launch_rd(const RdArgs& a, int grid, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_rcab_d<T, DEFER, TRAIN, BWD, GC, SEB>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, RD_LDS);
-        attr = true;
-    }
+    fen_detail::opt_in_lds<k_rcab_d<T, DEFER, TRAIN, BWD, GC, SEB>>(RD_LDS);
     hipLaunchKernelGGL((k_rcab_d<T, DEFER, TRAIN, BWD, GC, SEB>), dim3(grid), dim3(512), RD_LDS, s, a);
 }
 
@@ -1062,15 +1055,8 @@ void launch_rd_t(const fen_rcab_deferred_desc* d, int grid, hipStream_t s) {
     }
 }
 
-int rd_num_cus() {
-    if (g_cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (g_cus <= 0) g_cus = 256;
-    }
-    return g_cus;
-}
+// one block per CU, at most one per 16 x 16 tile
+int rd_grid(int B, int H, int W) { return fen_detail::persistent_grid(B * (H / 16) * (W / 16), 1); }
 
 }  // namespace
 
@@ -1080,29 +1066,27 @@ extern "C" int fen_rcab_deferred_supported(int dtype, int B, int H, int W, int C
         return 0;
     if ((size_t)B * H * W * 128 >= (size_t)0x7fff0000) return 0;   // 32-bit buffer offsets
     const size_t ntiles = (size_t)B * (H / 16) * (W / 16);
-    return ntiles <= (size_t)MAXG * rd_num_cus() ? 1 : 0;          // gates precomputed per block
+    return ntiles <= (size_t)MAXG * fen_detail::num_cus() ? 1 : 0;   // gates precomputed per block
 }
 
 extern "C" int fen_rcab_deferred(const fen_rcab_deferred_desc* d, void* stream) {
     if (!d || !d->x || !d->w1 || !d->w2 || !d->b1 || !d->b2 || !d->alpha || !d->t || !d->part) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(d->dtype)) return st;
     if (!fen_rcab_deferred_supported(d->dtype, d->B, d->H, d->W, d->C, d->Cr)) return FEN_EUNSUPPORTED;
     if (d->tp && (!d->pp || !d->pfc1 || !d->pfc2 || !d->xo)) return FEN_EINVAL;
     if ((d->z1 != nullptr) != (d->a1 != nullptr)) return FEN_EINVAL;
-    const int ncu = rd_num_cus();
-    const int ntiles = d->B * (d->H / 16) * (d->W / 16);
-    const int grid = ntiles < ncu ? ntiles : ncu;
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == FEN_F16) launch_rd_t<f16>(d, grid, s);
-    else launch_rd_t<bf16>(d, grid, s);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    const int grid = rd_grid(d->B, d->H, d->W);
+    return fen_detail::with_dtype16(d->dtype, [&](auto tag) -> int {
+        launch_rd_t<decltype(tag)>(d, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_rcab_bwd_se_supported(int dtype, int B, int H, int W, int C, int Cr) {
     if (!fen_rcab_deferred_supported(dtype, B, H, W, C, Cr)) return 0;
-    const int ncu = rd_num_cus();
     const int ntiles = B * (H / 16) * (W / 16);
-    const int grid = ntiles < ncu ? ntiles : ncu;
+    const int grid = rd_grid(B, H, W);
     return (ntiles + grid - 1) / grid <= 6 && (H / 16) * (W / 16) <= 64 ? 1 : 0;
 }
 
@@ -1110,6 +1094,7 @@ extern "C" int fen_rcab_bwd(const fen_rcab_bwd_desc* b, void* stream) {
     if (!b || !b->dt || !b->w2t || !b->w1t || !b->z1 || !b->alpha || !b->dz1 || !b->dalpha_part || !b->dx ||
         !b->dy)
         return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(b->dtype)) return st;
     if ((b->dot_t != nullptr) != (b->dot_part != nullptr)) return FEN_EINVAL;
     if (b->dres && b->dot_t) return FEN_EINVAL;       // the second residual takes the DOT operand's slot
     const bool seb = b->se_part != nullptr;
@@ -1119,9 +1104,7 @@ extern "C" int fen_rcab_bwd(const fen_rcab_bwd_desc* b, void* stream) {
     if (!fen_rcab_deferred_supported(b->dtype, b->B, b->H, b->W, b->C, Cr)) return FEN_EUNSUPPORTED;
     // SEB: <= 6 tiles per block (gate rows 4..15 hold their s, g), <= 64 tiles per image
     if (seb && !fen_rcab_bwd_se_supported(b->dtype, b->B, b->H, b->W, b->C, Cr)) return FEN_EUNSUPPORTED;
-    const int ncu = rd_num_cus();
-    const int ntiles = b->B * (b->H / 16) * (b->W / 16);
-    const int grid = ntiles < ncu ? ntiles : ncu;
+    const int grid = rd_grid(b->B, b->H, b->W);
     RdArgs a{};
     fen_rcab_deferred_desc& d = a.d;
     d.dtype = b->dtype;
@@ -1151,21 +1134,19 @@ extern "C" int fen_rcab_bwd(const fen_rcab_bwd_desc* b, void* stream) {
         a.se_dw1p = b->se_dw1p;
         a.se_dw2p = b->se_dw2p;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (seb) {
-        if (b->dtype == FEN_F16) launch_rd<f16, false, false, true, false, true>(a, grid, s);
-        else launch_rd<bf16, false, false, true, false, true>(a, grid, s);
-    } else {
-        if (b->dtype == FEN_F16) launch_rd<f16, false, false, true>(a, grid, s);
-        else launch_rd<bf16, false, false, true>(a, grid, s);
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype16(b->dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if (seb) launch_rd<T, false, false, true, false, true>(a, grid, (hipStream_t)stream);
+        else launch_rd<T, false, false, true>(a, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_rcab_group_end(const fen_rcab_deferred_desc* d, const void* w, const float* bias, const void* res,
                                   void* out, void* stream) {
     if (!d || !d->x || !d->tp || !d->pp || !d->pfc1 || !d->pfc2 || !w || !bias || !res || !out) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(d->dtype)) return st;
     if (!fen_rcab_deferred_supported(d->dtype, d->B, d->H, d->W, d->C, d->Cr)) return FEN_EUNSUPPORTED;
     RdArgs a{};
     a.d = *d;
@@ -1177,12 +1158,10 @@ extern "C" int fen_rcab_group_end(const fen_rcab_deferred_desc* d, const void* w
     a.d.part = nullptr;
     a.d.z1 = a.d.a1 = nullptr;
     a.gres = res;
-    const int ncu = rd_num_cus();
-    const int ntiles = d->B * (d->H / 16) * (d->W / 16);
-    const int grid = ntiles < ncu ? ntiles : ncu;
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == FEN_F16) launch_rd<f16, true, false, false, true>(a, grid, s);
-    else launch_rd<bf16, true, false, false, true>(a, grid, s);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    const int grid = rd_grid(d->B, d->H, d->W);
+    return fen_detail::with_dtype16(d->dtype, [&](auto tag) -> int {
+        launch_rd<decltype(tag), true, false, false, true>(a, grid, (hipStream_t)stream);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }

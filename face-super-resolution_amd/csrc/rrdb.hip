@@ -256,8 +256,6 @@ int dispatch_rrdb(const fen_rrdb_conv_desc* d, hipStream_t s) {
     return launch_rrdb<T, 16>(d, s);
 }
 
-bool dtype_ok(int dtype) { return dtype == FEN_F32 || dtype == FEN_BF16 || dtype == FEN_F16; }
-
 // pixel indices and the grid's x dimension are ints in the kernels
 bool pixels_ok(int B, int H, int W) { return (size_t)B * (size_t)H * (size_t)W < ((size_t)1 << 31); }
 
@@ -266,7 +264,7 @@ bool pixels_ok(int B, int H, int W) { return (size_t)B * (size_t)H * (size_t)W <
 extern "C" int fen_rrdb_conv(const fen_rrdb_conv_desc* d, void* stream) {
     if (!d || !d->x || !d->w || !d->bias || !d->y) return FEN_EINVAL;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return FEN_EINVAL;
-    if (!dtype_ok(d->dtype)) return FEN_EINVAL;
+    if (fen_detail::check_dtype(d->dtype) != FEN_OK) return FEN_EINVAL;
     if (((uintptr_t)d->x | (uintptr_t)d->w | (uintptr_t)d->y | (uintptr_t)d->r1 | (uintptr_t)d->r2) & 15) return FEN_EINVAL;
     const int esz = d->dtype == FEN_F32 ? 4 : 2;
     // the network's channel counts only: inputs 64 + 32 j, outputs 32 / 64, or <= 16 planes of NCHW fp32
@@ -281,12 +279,7 @@ extern "C" int fen_rrdb_conv(const fen_rrdb_conv_desc* d, void* stream) {
     // in place (a dense block's conv 1..4): the written slice lies past every channel read
     if (d->x == d->y && (d->nchw_out || d->y_off < d->Cin)) return FEN_EINVAL;
     if (!pixels_ok(d->B, d->H, d->W)) return FEN_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    switch (d->dtype) {
-        case FEN_BF16: return dispatch_rrdb<bf16>(d, s);
-        case FEN_F16: return dispatch_rrdb<f16>(d, s);
-        default: return dispatch_rrdb<float>(d, s);
-    }
+    return fen_detail::with_dtype(d->dtype, [&](auto tag) { return dispatch_rrdb<decltype(tag)>(d, (hipStream_t)stream); });
 }
 
 extern "C" int fen_rrdb_block(const fen_rrdb_block_desc* d, void* stream) {
@@ -294,7 +287,7 @@ extern "C" int fen_rrdb_block(const fen_rrdb_block_desc* d, void* stream) {
     for (int k = 0; k < 5; ++k)
         if (!d->w[k] || !d->bias[k]) return FEN_EINVAL;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->num_feat <= 0 || d->num_grow_ch <= 0) return FEN_EINVAL;
-    if (!dtype_ok(d->dtype)) return FEN_EINVAL;
+    if (fen_detail::check_dtype(d->dtype) != FEN_OK) return FEN_EINVAL;
     if (d->next == d->buf || (d->x_rrdb && d->x_rrdb == d->next)) return FEN_EINVAL;
     if (d->num_feat != RRDB_FEAT || d->num_grow_ch != RRDB_GROW) return FEN_EUNSUPPORTED;
     if (!pixels_ok(d->B, d->H, d->W)) return FEN_EUNSUPPORTED;
@@ -325,22 +318,15 @@ extern "C" int fen_rrdb_block(const fen_rrdb_block_desc* d, void* stream) {
 extern "C" int fen_rrdb_first(int dtype, int B, int Ci, int H, int W, const float* x, const float* w,
                               const float* bias, void* y, int y_stride, void* y2, void* stream) {
     if (!x || !w || !bias || !y || B <= 0 || Ci <= 0 || H <= 0 || W <= 0) return FEN_EINVAL;
-    if (!dtype_ok(dtype) || y_stride < RRDB_FEAT || y_stride % 4) return FEN_EINVAL;
+    if (fen_detail::check_dtype(dtype) != FEN_OK || y_stride < RRDB_FEAT || y_stride % 4) return FEN_EINVAL;
     if (Ci > 8 || !pixels_ok(B, H, W)) return FEN_EUNSUPPORTED;
     const size_t nthr = (size_t)B * H * W * 16;
     const unsigned nb = (unsigned)((nthr + 255) / 256);
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case FEN_BF16:
-            hipLaunchKernelGGL(k_rrdb_first<bf16>, dim3(nb), dim3(256), 0, s, B, Ci, H, W, x, w, bias, (bf16*)y, y_stride, (bf16*)y2);
-            break;
-        case FEN_F16:
-            hipLaunchKernelGGL(k_rrdb_first<f16>, dim3(nb), dim3(256), 0, s, B, Ci, H, W, x, w, bias, (f16*)y, y_stride, (f16*)y2);
-            break;
-        default:
-            hipLaunchKernelGGL(k_rrdb_first<float>, dim3(nb), dim3(256), 0, s, B, Ci, H, W, x, w, bias, (float*)y, y_stride, (float*)y2);
-            break;
-    }
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_rrdb_first<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, B, Ci, H, W, x, w, bias, (T*)y,
+                           y_stride, (T*)y2);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }

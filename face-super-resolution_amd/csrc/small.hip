@@ -1940,64 +1940,38 @@ extern "C" int fen_conv_first_fwd_ex(int dtype, int B, int Ci, int H, int W, int
     if (!x || !w || !bias || !y || B <= 0 || Ci <= 0 || Ci > 3 || C % 8 || C > 128) return FEN_EINVAL;
     const size_t n = (size_t)B * H * W * (C / 8);
     const size_t lds = (size_t)Ci * 9 * C * sizeof(float);
-    static int m16 = -1;                                 // FEN_CF_M16=0: the VALU forms (A/B runs)
-    if (m16 < 0) {
-        const char* e = getenv("FEN_CF_M16");
-        m16 = e ? atoi(e) : 1;
-    }
-    if (m16 && (dtype == FEN_BF16 || dtype == FEN_F16) && (C == 16 || C == 32 || C == 64 || C == 128)) {
-        const int ntiles = B * ((H + 15) >> 4) * ((W + 15) >> 4);
-        const unsigned nb = (unsigned)std::min(ntiles, CFM16_BLOCKS);
-#define CFM16_LAUNCH(TT, MBv)                                                                                   \
-    hipLaunchKernelGGL((k_conv_first_m16<TT, MBv>), dim3(nb), dim3(256), 0, STREAM, B, Ci, H, W, C, x, w, bias, \
-                       (TT*)y, in_mean, in_istd, act)
-#define CFM16_MB(TT)                      \
-    switch (C / 16) {                     \
-        case 1: CFM16_LAUNCH(TT, 1); break; \
-        case 2: CFM16_LAUNCH(TT, 2); break; \
-        case 4: CFM16_LAUNCH(TT, 4); break; \
-        default: CFM16_LAUNCH(TT, 8); break; \
-    }
-        if (dtype == FEN_BF16) {
-            CFM16_MB(bf16);
-        } else {
-            CFM16_MB(f16);
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if constexpr (sizeof(T) == 2) {
+            if (C == 16 || C == 32 || C == 64 || C == 128) {   // the MFMA form
+                const int ntiles = B * ((H + 15) >> 4) * ((W + 15) >> 4);
+                const unsigned nb = (unsigned)std::min(ntiles, CFM16_BLOCKS);
+                auto go = [&](auto mb) {
+                    hipLaunchKernelGGL((k_conv_first_m16<T, decltype(mb)::value>), dim3(nb), dim3(256), 0, STREAM, B, Ci,
+                                       H, W, C, x, w, bias, (T*)y, in_mean, in_istd, act);
+                };
+                switch (C / 16) {
+                    case 1: go(std::integral_constant<int, 1>{}); break;
+                    case 2: go(std::integral_constant<int, 2>{}); break;
+                    case 4: go(std::integral_constant<int, 4>{}); break;
+                    default: go(std::integral_constant<int, 8>{}); break;
+                }
+                FEN_CHECK_LAUNCH();
+                return FEN_OK;
+            }
         }
-#undef CFM16_MB
-#undef CFM16_LAUNCH
+        if (W % 4 == 0) {
+            const unsigned nb = (unsigned)((size_t)B * ((H + 1) / 2) * ((W + CF4_TW - 1) / CF4_TW));
+            const size_t lds4 = lds + (size_t)Ci * 4 * (CF4_TW + 2) * sizeof(float);
+            hipLaunchKernelGGL(k_conv_first4<T>, dim3(nb), dim3(256), lds4, STREAM, B, Ci, H, W, C, x, w, bias, (T*)y,
+                               in_mean, in_istd, act);
+        } else {
+            hipLaunchKernelGGL(k_conv_first<T>, dim3(nblk(n)), dim3(256), lds, STREAM, B, Ci, H, W, C, x, w, bias, (T*)y,
+                               in_mean, in_istd, act);
+        }
         FEN_CHECK_LAUNCH();
         return FEN_OK;
-    }
-    if (W % 4 == 0) {
-        const unsigned nb = (unsigned)((size_t)B * ((H + 1) / 2) * ((W + CF4_TW - 1) / CF4_TW));
-        const size_t lds4 = lds + (size_t)Ci * 4 * (CF4_TW + 2) * sizeof(float);
-        if (dtype == FEN_BF16)
-            hipLaunchKernelGGL(k_conv_first4<bf16>, dim3(nb), dim3(256), lds4, STREAM, B, Ci, H, W, C, x, w, bias,
-                               (bf16*)y, in_mean, in_istd, act);
-        else if (dtype == FEN_F16)
-            hipLaunchKernelGGL(k_conv_first4<f16>, dim3(nb), dim3(256), lds4, STREAM, B, Ci, H, W, C, x, w, bias,
-                               (f16*)y, in_mean, in_istd, act);
-        else if (dtype == FEN_F32)
-            hipLaunchKernelGGL(k_conv_first4<float>, dim3(nb), dim3(256), lds4, STREAM, B, Ci, H, W, C, x, w, bias,
-                               (float*)y, in_mean, in_istd, act);
-        else
-            return FEN_EINVAL;
-        FEN_CHECK_LAUNCH();
-        return FEN_OK;
-    }
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_conv_first<bf16>, dim3(nblk(n)), dim3(256), lds, STREAM, B, Ci, H, W, C, x, w, bias,
-                           (bf16*)y, in_mean, in_istd, act);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_conv_first<f16>, dim3(nblk(n)), dim3(256), lds, STREAM, B, Ci, H, W, C, x, w, bias,
-                           (f16*)y, in_mean, in_istd, act);
-    else if (dtype == FEN_F32)
-        hipLaunchKernelGGL(k_conv_first<float>, dim3(nblk(n)), dim3(256), lds, STREAM, B, Ci, H, W, C, x, w, bias,
-                           (float*)y, in_mean, in_istd, act);
-    else
-        return FEN_EINVAL;
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    });
 }
 
 extern "C" int fen_conv_first_fwd(int dtype, int B, int Ci, int H, int W, int C, const float* x, const float* w,
@@ -2012,48 +1986,25 @@ extern "C" size_t fen_conv_first_work_floats(int B, int Ci, int H, int W, int C)
 extern "C" int fen_conv_first_wgrad(int dtype, int B, int Ci, int H, int W, int C, const float* x, const void* dy,
                                     float* dw, float* db, int accumulate, float* work, void* stream) {
     if (!x || !dy || !dw || !work || Ci > 3 || C > 128 || B <= 0) return FEN_EINVAL;
-    if (C % 16 == 0) {   // (the VALU form below: 223 vs ~70 us at 256x256, B=32; kept for odd C)
-        // matrix-core form: MB = 16-channel blocks (C = 32, 64 or 128 on the path)
-        auto go = [&](auto tag, auto mb) {
-            using TT = decltype(tag);
-            constexpr int MBv = decltype(mb)::value;
-            hipLaunchKernelGGL((k_conv_first_wgrad_m<TT, MBv>), dim3(CF_BLOCKS), dim3(256), 0, STREAM, B, Ci, H, W, C, x,
-                               (const TT*)dy, work);
-        };
-        const int mb = C <= 32 ? 2 : C <= 64 ? 4 : 8;
-        if (dtype == FEN_BF16) {
-            if (mb == 2) go(bf16{}, std::integral_constant<int, 2>{});
-            else if (mb == 4) go(bf16{}, std::integral_constant<int, 4>{});
-            else go(bf16{}, std::integral_constant<int, 8>{});
-        } else if (dtype == FEN_F16) {
-            if (mb == 2) go(f16{}, std::integral_constant<int, 2>{});
-            else if (mb == 4) go(f16{}, std::integral_constant<int, 4>{});
-            else go(f16{}, std::integral_constant<int, 8>{});
-        } else if (dtype == FEN_F32) {
-            if (mb == 2) go(float{}, std::integral_constant<int, 2>{});
-            else if (mb == 4) go(float{}, std::integral_constant<int, 4>{});
-            else go(float{}, std::integral_constant<int, 8>{});
+    const int rc = fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if (C % 16 == 0) {   // (the VALU form below: 223 vs ~70 us at 256x256, B=32; kept for odd C)
+            // matrix-core form: MB = 16-channel blocks (C = 32, 64 or 128 on the path)
+            auto go = [&](auto mb) {
+                hipLaunchKernelGGL((k_conv_first_wgrad_m<T, decltype(mb)::value>), dim3(CF_BLOCKS), dim3(256), 0, STREAM,
+                                   B, Ci, H, W, C, x, (const T*)dy, work);
+            };
+            if (C <= 32) go(std::integral_constant<int, 2>{});
+            else if (C <= 64) go(std::integral_constant<int, 4>{});
+            else go(std::integral_constant<int, 8>{});
         } else {
-            return FEN_EINVAL;
+            hipLaunchKernelGGL(k_conv_first_wgrad<T>, dim3(CF_BLOCKS), dim3(256), 0, STREAM, B, Ci, H, W, C, x,
+                               (const T*)dy, work);
         }
         FEN_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_conv_first_finalize, dim3(28), dim3(1024), 0, STREAM, CF_BLOCKS, Ci, C, work,
-                           dw, db, accumulate);
-        FEN_CHECK_LAUNCH();
         return FEN_OK;
-    }
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_conv_first_wgrad<bf16>, dim3(CF_BLOCKS), dim3(256), 0, STREAM, B, Ci, H, W, C, x,
-                           (const bf16*)dy, work);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_conv_first_wgrad<f16>, dim3(CF_BLOCKS), dim3(256), 0, STREAM, B, Ci, H, W, C, x,
-                           (const f16*)dy, work);
-    else if (dtype == FEN_F32)
-        hipLaunchKernelGGL(k_conv_first_wgrad<float>, dim3(CF_BLOCKS), dim3(256), 0, STREAM, B, Ci, H, W, C, x,
-                           (const float*)dy, work);
-    else
-        return FEN_EINVAL;
-    FEN_CHECK_LAUNCH();
+    });
+    if (rc != FEN_OK) return rc;
     hipLaunchKernelGGL(k_conv_first_finalize, dim3(28), dim3(1024), 0, STREAM, CF_BLOCKS, Ci, C, work, dw, db,
                        accumulate);
     FEN_CHECK_LAUNCH();
@@ -2074,16 +2025,16 @@ extern "C" int fen_conv_last_bwd(int dtype, int B, int H, int W, int C, int Co, 
                                  const void* pre, const void* post, const float* alpha, void* du, float* dal_part,
                                  float* dw_part, float* db_part, void* stream) {
     if (!dout || !w || !pre || !post || !alpha || !du || !dal_part || !dw_part || !db_part) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(dtype)) return st;
     if (!fen_conv_last_bwd_supported(dtype, B, H, W, C, Co)) return FEN_EUNSUPPORTED;
     const int nb = (int)fen_conv_last_dgrad_part_rows(B, H, W);
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_cl_bwd<bf16>, dim3(nb), dim3(256), 0, STREAM, B, H, W, Co, (const bf16*)dout, w,
-                           (const bf16*)pre, (const bf16*)post, alpha, (bf16*)du, dal_part, dw_part, db_part);
-    else
-        hipLaunchKernelGGL(k_cl_bwd<f16>, dim3(nb), dim3(256), 0, STREAM, B, H, W, Co, (const f16*)dout, w,
-                           (const f16*)pre, (const f16*)post, alpha, (f16*)du, dal_part, dw_part, db_part);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype16(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_cl_bwd<T>, dim3(nb), dim3(256), 0, STREAM, B, H, W, Co, (const T*)dout, w, (const T*)pre,
+                           (const T*)post, alpha, (T*)du, dal_part, dw_part, db_part);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_conv_last_dgrad(int dtype, int B, int H, int W, int C, int Co, const void* dout, const float* w,
@@ -2092,12 +2043,13 @@ extern "C" int fen_conv_last_dgrad(int dtype, int B, int H, int W, int C, int Co
     if (!dout || !w || !pre || !alpha || !du || !part || Co > 3 || C < 32 || C > 256 || 256 % (C / 2) || (H | W) & 1)
         return FEN_EINVAL;
     const int nb = (int)fen_conv_last_dgrad_part_rows(B, H, W);
-    auto launch = [&](auto tag) -> int {
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
         using T = decltype(tag);
         if constexpr (sizeof(T) == 2) {
             if (C == 64 && H % 16 == 0 && W % 16 == 0) {
                 hipLaunchKernelGGL((k_cld_p<T>), dim3(nb), dim3(256), 0, STREAM, B, H, W, Co, (const T*)dout, w,
                                    (const T*)pre, (const T*)post, alpha, (T*)du, part);
+                FEN_CHECK_LAUNCH();
                 return FEN_OK;
             }
         }
@@ -2112,16 +2064,9 @@ extern "C" int fen_conv_last_dgrad(int dtype, int B, int H, int W, int C, int Co
             case 256: go(k_conv_last_dgrad<T, 256>); break;
             default: return FEN_EINVAL;
         }
+        FEN_CHECK_LAUNCH();
         return FEN_OK;
-    };
-    int rc;
-    if (dtype == FEN_BF16) rc = launch(bf16{});
-    else if (dtype == FEN_F16) rc = launch(f16{});
-    else if (dtype == FEN_F32) rc = launch(0.f);
-    else return FEN_EINVAL;
-    if (rc != FEN_OK) return rc;
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    });
 }
 
 static bool se_shape_ok(int C, int Cr) { return C > 0 && C <= 256 && C % 16 == 0 && Cr > 0 && Cr <= 64 && Cr % 4 == 0; }
@@ -2138,20 +2083,16 @@ extern "C" int fen_se_fwd(int B, int C, int Cr, int nparts, float inv_hw, const 
 extern "C" int fen_se_apply(int dtype, int B, int HW, int C, const void* t, const float* s, float res_scale,
                             const void* x, void* y, void* stream) {
     if (!t || !s || !x || !y) return FEN_EINVAL;
-    const int V = dtype == FEN_F32 ? 4 : 8;
-    if (C % V) return FEN_EUNSUPPORTED;
-    const size_t nvec = (size_t)B * HW * C / V;
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL((k_se_apply<bf16, false>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C,
-                           (const bf16*)t, s, res_scale, x, (bf16*)y);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL((k_se_apply<f16, false>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C,
-                           (const f16*)t, s, res_scale, x, (f16*)y);
-    else
-        hipLaunchKernelGGL((k_se_apply<float, false>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C,
-                           (const float*)t, s, res_scale, x, (float*)y);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        constexpr int V = Tr<T>::EPC;
+        if (C % V) return FEN_EUNSUPPORTED;
+        const size_t nvec = (size_t)B * HW * C / V;
+        hipLaunchKernelGGL((k_se_apply<T, false>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C, (const T*)t, s,
+                           res_scale, x, (T*)y);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_se_fused(int dtype, int B, int HW, int C, int Cr, int nparts, float inv_hw, const float* part,
@@ -2159,24 +2100,17 @@ extern "C" int fen_se_fused(int dtype, int B, int HW, int C, int Cr, int nparts,
                             float res_scale, const void* x, void* y, void* stream) {
     if (!part || !w1 || !w2 || !t || !x || !y || B <= 0 || HW <= 0 || nparts <= 0) return FEN_EINVAL;
     if (!se_shape_ok(C, Cr) || C * Cr > 4096) return FEN_EUNSUPPORTED;
-    const int V = dtype == FEN_F32 ? 4 : 8;
-    const size_t nv = (size_t)HW * C / V;
-    // 8 vectors per thread: 16 blocks per 64x64x64 bf16 image -> 512 blocks at B = 32
-    constexpr int NPT = 8;
-    const unsigned splits = (unsigned)((nv + 256 * NPT - 1) / (256 * NPT));
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL((k_se_fused<bf16, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw,
-                           part, w1, w2, mean, hid, s, (const bf16*)t, res_scale, (const bf16*)x, (bf16*)y);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL((k_se_fused<f16, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw,
-                           part, w1, w2, mean, hid, s, (const f16*)t, res_scale, (const f16*)x, (f16*)y);
-    else if (dtype == FEN_F32)
-        hipLaunchKernelGGL((k_se_fused<float, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw,
-                           part, w1, w2, mean, hid, s, (const float*)t, res_scale, (const float*)x, (float*)y);
-    else
-        return FEN_EINVAL;
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        const size_t nv = (size_t)HW * C / Tr<T>::EPC;
+        // 8 vectors per thread: 16 blocks per 64x64x64 bf16 image -> 512 blocks at B = 32
+        constexpr int NPT = 8;
+        const unsigned splits = (unsigned)((nv + 256 * NPT - 1) / (256 * NPT));
+        hipLaunchKernelGGL((k_se_fused<T, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw, part,
+                           w1, w2, mean, hid, s, (const T*)t, res_scale, (const T*)x, (T*)y);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 // pixels per pool_dot block: 64 (HW = 4096 -> 64 chunks x B images = 2048 blocks, ~32 waves
@@ -2194,20 +2128,16 @@ extern "C" size_t fen_pool_parts(int HW) {
 
 extern "C" int fen_pool_dot(int dtype, int B, int HW, int C, const void* a, const void* b_, float* part,
                             void* stream) {
-    const int V = dtype == FEN_F32 ? 4 : 8;
-    if (!a || !part || C % V || C / V > 256) return FEN_EINVAL;
-    const int nchunk = (int)fen_pool_parts(HW);
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_pool_dot<bf16>, dim3(nchunk, B), dim3(256), 0, STREAM, HW, C, nchunk, (const bf16*)a,
-                           (const bf16*)b_, part);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_pool_dot<f16>, dim3(nchunk, B), dim3(256), 0, STREAM, HW, C, nchunk, (const f16*)a,
-                           (const f16*)b_, part);
-    else
-        hipLaunchKernelGGL(k_pool_dot<float>, dim3(nchunk, B), dim3(256), 0, STREAM, HW, C, nchunk, (const float*)a,
-                           (const float*)b_, part);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        constexpr int V = Tr<T>::EPC;
+        if (!a || !part || C % V || C / V > 256) return FEN_EINVAL;
+        const int nchunk = (int)fen_pool_parts(HW);
+        hipLaunchKernelGGL(k_pool_dot<T>, dim3(nchunk, B), dim3(256), 0, STREAM, HW, C, nchunk, (const T*)a,
+                           (const T*)b_, part);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_se_bwd(int B, int C, int Cr, int nparts, float inv_hw, float res_scale, const float* part,
@@ -2227,20 +2157,16 @@ extern "C" int fen_se_bwd(int B, int C, int Cr, int nparts, float inv_hw, float 
 extern "C" int fen_se_bwd_apply(int dtype, int B, int HW, int C, const void* dy, const float* s, float res_scale,
                                 const float* g, void* dt, void* stream) {
     if (!dy || !s || !g || !dt) return FEN_EINVAL;
-    const int V = dtype == FEN_F32 ? 4 : 8;
-    if (C % V) return FEN_EUNSUPPORTED;
-    const size_t nvec = (size_t)B * HW * C / V;
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL((k_se_apply<bf16, true>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C,
-                           (const bf16*)dy, s, res_scale, (const void*)g, (bf16*)dt);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL((k_se_apply<f16, true>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C,
-                           (const f16*)dy, s, res_scale, (const void*)g, (f16*)dt);
-    else
-        hipLaunchKernelGGL((k_se_apply<float, true>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C,
-                           (const float*)dy, s, res_scale, (const void*)g, (float*)dt);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        constexpr int V = Tr<T>::EPC;
+        if (C % V) return FEN_EUNSUPPORTED;
+        const size_t nvec = (size_t)B * HW * C / V;
+        hipLaunchKernelGGL((k_se_apply<T, true>), dim3(nblk(nvec)), dim3(256), 0, STREAM, nvec, HW, C, (const T*)dy, s,
+                           res_scale, (const void*)g, (T*)dt);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_se_bwd_fused(int dtype, int B, int HW, int C, int Cr, int nparts, float inv_hw, float res_scale,
@@ -2249,25 +2175,20 @@ extern "C" int fen_se_bwd_fused(int dtype, int B, int HW, int C, int Cr, int npa
                                 void* dt, void* stream) {
     if (!part || !mean || !hid || !s || !w1 || !w2 || !dy || !dw1p || !dw2p || !dt || B <= 0 || HW <= 0)
         return FEN_EINVAL;
-    const int V = dtype == FEN_F32 ? 4 : 8;
-    if (C <= 0 || C > 64 || C % V || Cr <= 0 || Cr > 64 || C * Cr > 4096 || (C * Cr) % 4 || nparts <= 0 || nparts > 64)
-        return FEN_EUNSUPPORTED;
-    const size_t nv = (size_t)HW * C / V;
-    constexpr int NPT = 8;
-    const unsigned splits = (unsigned)((nv + 256 * NPT - 1) / (256 * NPT));
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL((k_se_bwd_fused<bf16, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw,
-                           res_scale, part, mean, hid, s, w1, w2, (const bf16*)dy, g, dw1p, dw2p, (bf16*)dt);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL((k_se_bwd_fused<f16, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw,
-                           res_scale, part, mean, hid, s, w1, w2, (const f16*)dy, g, dw1p, dw2p, (f16*)dt);
-    else if (dtype == FEN_F32)
-        hipLaunchKernelGGL((k_se_bwd_fused<float, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts,
-                           inv_hw, res_scale, part, mean, hid, s, w1, w2, (const float*)dy, g, dw1p, dw2p, (float*)dt);
-    else
-        return FEN_EINVAL;
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        constexpr int V = Tr<T>::EPC;
+        if (C <= 0 || C > 64 || C % V || Cr <= 0 || Cr > 64 || C * Cr > 4096 || (C * Cr) % 4 || nparts <= 0 ||
+            nparts > 64)
+            return FEN_EUNSUPPORTED;
+        const size_t nv = (size_t)HW * C / V;
+        constexpr int NPT = 8;
+        const unsigned splits = (unsigned)((nv + 256 * NPT - 1) / (256 * NPT));
+        hipLaunchKernelGGL((k_se_bwd_fused<T, NPT>), dim3(splits, B), dim3(256), 0, STREAM, HW, C, Cr, nparts, inv_hw,
+                           res_scale, part, mean, hid, s, w1, w2, (const T*)dy, g, dw1p, dw2p, (T*)dt);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_bicubic_down4(int B, int C, int H, int W, const float* hr, float* lr, void* stream) {
@@ -2315,16 +2236,12 @@ extern "C" size_t fen_packed_elems(int mode, int Cout, int Cin) {
 extern "C" int fen_pack_conv_w(int dtype, int mode, int Cout, int Cin, const float* w, void* out, void* stream) {
     if (!w || !out || mode < 0 || mode > 2 || (mode == 1 && Cout % 4)) return FEN_EINVAL;
     const size_t n = fen_packed_elems(mode, Cout, Cin);
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_pack<bf16>, dim3(nblk(n)), dim3(256), 0, STREAM, mode, Cout, Cin, w, (bf16*)out, n);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_pack<f16>, dim3(nblk(n)), dim3(256), 0, STREAM, mode, Cout, Cin, w, (f16*)out, n);
-    else if (dtype == FEN_F32)
-        hipLaunchKernelGGL(k_pack<float>, dim3(nblk(n)), dim3(256), 0, STREAM, mode, Cout, Cin, w, (float*)out, n);
-    else
-        return FEN_EINVAL;
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_pack<T>, dim3(nblk(n)), dim3(256), 0, STREAM, mode, Cout, Cin, w, (T*)out, n);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" size_t fen_pack_table_bytes(int njobs) {
@@ -2332,7 +2249,8 @@ extern "C" size_t fen_pack_table_bytes(int njobs) {
 }
 
 extern "C" int fen_pack_table(int dtype, int njobs, const fen_pack_job* jobs, void* table_host, size_t* total) {
-    if (njobs <= 0 || !jobs || !table_host || !total || (dtype != FEN_BF16 && dtype != FEN_F16 && dtype != FEN_F32)) return FEN_EINVAL;
+    if (njobs <= 0 || !jobs || !table_host || !total || fen_detail::check_dtype(dtype) != FEN_OK)
+        return FEN_EINVAL;
     PackJobK* pj = (PackJobK*)table_host;
     unsigned long long* e0 = (unsigned long long*)(pj + njobs);
     unsigned long long acc = 0;
@@ -2355,30 +2273,24 @@ extern "C" int fen_pack_multi(int dtype, int njobs, const void* table_dev, size_
     const PackJobK* pj = (const PackJobK*)table_dev;
     const unsigned long long* e0 = (const unsigned long long*)(pj + njobs);
     const unsigned nb = (unsigned)((total + PACK_BLK - 1) / PACK_BLK);   // 256 threads x PACK_RUN
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_pack_multi<bf16>, dim3(nb), dim3(256), 0, STREAM, njobs, pj, e0, (unsigned long long)total);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_pack_multi<f16>, dim3(nb), dim3(256), 0, STREAM, njobs, pj, e0, (unsigned long long)total);
-    else if (dtype == FEN_F32)
-        hipLaunchKernelGGL(k_pack_multi<float>, dim3(nb), dim3(256), 0, STREAM, njobs, pj, e0, (unsigned long long)total);
-    else
-        return FEN_EINVAL;
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_pack_multi<T>, dim3(nb), dim3(256), 0, STREAM, njobs, pj, e0, (unsigned long long)total);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_nchw_to_nhwc(int dtype, int B, int C, int H, int W, int Cpad, const float* x, void* y,
                                 void* stream) {
     if (!x || !y || Cpad < C) return FEN_EINVAL;
     const size_t n = (size_t)B * Cpad * H * W;
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_nchw_to_nhwc<bf16>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, Cpad, x, (bf16*)y);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_nchw_to_nhwc<f16>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, Cpad, x, (f16*)y);
-    else
-        hipLaunchKernelGGL(k_nchw_to_nhwc<float>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, Cpad, x, (float*)y);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_nchw_to_nhwc<T>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, Cpad, x, (T*)y);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_prelu_bwd_unshuffle(int dtype, int B, int H, int W, int C, const void* dy, const void* pre,
@@ -2386,30 +2298,24 @@ extern "C" int fen_prelu_bwd_unshuffle(int dtype, int B, int H, int W, int C, co
     if (!dy || !pre || !alpha || !du || !part || C < 32 || C > 256 || 256 % (C / 2) || (H | W) & 1)
         return FEN_EINVAL;
     const int nb = B * ((H + 15) / 16) * ((W + 15) / 16);
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_prelu_bwd_unshuffle<bf16>, dim3(nb), dim3(256), 0, STREAM, B, H, W, C, (const bf16*)dy,
-                           (const bf16*)pre, alpha, (bf16*)du, part);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_prelu_bwd_unshuffle<f16>, dim3(nb), dim3(256), 0, STREAM, B, H, W, C, (const f16*)dy,
-                           (const f16*)pre, alpha, (f16*)du, part);
-    else
-        hipLaunchKernelGGL(k_prelu_bwd_unshuffle<float>, dim3(nb), dim3(256), 0, STREAM, B, H, W, C,
-                           (const float*)dy, (const float*)pre, alpha, (float*)du, part);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_prelu_bwd_unshuffle<T>, dim3(nb), dim3(256), 0, STREAM, B, H, W, C, (const T*)dy,
+                           (const T*)pre, alpha, (T*)du, part);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_nhwc_to_nchw(int dtype, int B, int C, int H, int W, const void* x, float* y, void* stream) {
     if (!x || !y) return FEN_EINVAL;
     const size_t n = (size_t)B * C * H * W;
-    if (dtype == FEN_BF16)
-        hipLaunchKernelGGL(k_nhwc_to_nchw<bf16>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, (const bf16*)x, y);
-    else if (dtype == FEN_F16)
-        hipLaunchKernelGGL(k_nhwc_to_nchw<f16>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, (const f16*)x, y);
-    else
-        hipLaunchKernelGGL(k_nhwc_to_nchw<float>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, (const float*)x, y);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(k_nhwc_to_nchw<T>, dim3(nblk(n)), dim3(256), 0, STREAM, B, C, H, W, (const T*)x, y);
+        FEN_CHECK_LAUNCH();
+        return FEN_OK;
+    });
 }
 
 extern "C" int fen_sumsq_parts(size_t n) {
@@ -2473,7 +2379,25 @@ extern "C" int fen_scale(size_t n, float* y, float s, void* stream) {
 
 namespace fen_detail {
 thread_local int last_hip_error = 0;
+
+int device_slot() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
+    return dev;
 }
+
+int num_cus() {
+    static int cus[MAX_DEVICES] = {};
+    int& n = cus[device_slot()];
+    if (n == 0) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        if (n <= 0) n = 256;
+    }
+    return n;
+}
+}  // namespace fen_detail
 
 extern "C" const char* fen_last_hip_error(void) {
     const int e = fen_detail::last_hip_error;

@@ -492,6 +492,7 @@ extern "C" int fen_ssim(int dtype, int B, int C, int H, int W, const float* pred
     if (!pred || !target || !window1d || !part || B <= 0 || C <= 0 || H <= 0 || W <= 0) return FEN_EINVAL;
     if (window_size != 2 * SR + 1) return FEN_EUNSUPPORTED;
     if (grad_mode < 0 || grad_mode > 2 || (grad_mode && !grad) || (grad_mode == 2 && C > 16)) return FEN_EINVAL;
+    if (const int st = fen_detail::check_dtype(dtype)) return st;
     SsimWin w;
     for (int j = 0; j < 2 * SR + 1; ++j) w.g[j] = window1d[j];
     const dim3 grid((W + ST - 1) / ST, (H + ST - 1) / ST, B * C);
@@ -507,21 +508,22 @@ extern "C" int fen_ssim(int dtype, int B, int C, int H, int W, const float* pred
     } else if (grad_mode == 1) {
         hipLaunchKernelGGL((k_ssim<true, float, 1>), grid, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1, C2,
                            part, grad, grad_scale, grad_mode, nullptr);
-    } else if (C <= 3 && (dtype == FEN_F32 || dtype == FEN_BF16)) {
-        if (dtype == FEN_F32)
-            hipLaunchKernelGGL((k_ssim<true, float, 3>), gridb, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1,
-                               C2, part, grad, grad_scale, grad_mode, nullptr);
-        else
-            hipLaunchKernelGGL((k_ssim<true, bf16, 3>), gridb, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1,
-                               C2, part, grad, grad_scale, grad_mode, nullptr);
-    } else if (dtype == FEN_F32) {
-        hipLaunchKernelGGL((k_ssim<true, float, 1>), grid, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1, C2,
-                           part, grad, grad_scale, grad_mode, nullptr);
-    } else if (dtype == FEN_BF16) {
-        hipLaunchKernelGGL((k_ssim<true, bf16, 1>), grid, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1, C2,
-                           part, grad, grad_scale, grad_mode, nullptr);
-    } else {
-        return FEN_EINVAL;
+    } else {   // the gradient accumulated into a `dtype` buffer: f32 or bf16
+        return fen_detail::with_dtype(dtype, [&](auto tag) -> int {
+            using T = decltype(tag);
+            if constexpr (std::is_same<T, f16>::value) {
+                return FEN_EINVAL;
+            } else {
+                if (C <= 3)
+                    hipLaunchKernelGGL((k_ssim<true, T, 3>), gridb, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1,
+                                       C2, part, grad, grad_scale, grad_mode, nullptr);
+                else
+                    hipLaunchKernelGGL((k_ssim<true, T, 1>), grid, dim3(256), 0, STREAM, B, C, H, W, pred, target, w, C1,
+                                       C2, part, grad, grad_scale, grad_mode, nullptr);
+                FEN_CHECK_LAUNCH();
+                return FEN_OK;
+            }
+        });
     }
     FEN_CHECK_LAUNCH();
     return FEN_OK;

@@ -573,18 +573,6 @@ bool wgrad_use_p(const fen_wgrad_desc* d) {
            yb < 0x7fff0000u;
 }
 
-int wgrad_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    return cus;
-}
-
 // tiles per chunk / chunks per job for njobs jobs sharing ~256 blocks
 int wgrad_geom(const fen_wgrad_desc* d, int njobs, int* nchunk, int* tpc, int* cot) {
     const int tpi = ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
@@ -625,14 +613,6 @@ int launch_p(int n, const fen_wgrad_desc* ds, float* work, hipStream_t s) {
     const fen_wgrad_desc* d = &ds[0];
     int nchunk, tpc, cot;
     wgrad_geom(d, n, &nchunk, &tpc, &cot);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_wgrad_p<64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * WgCfg<64>::SLOT);
-        (void)hipFuncSetAttribute((const void*)k_wgrad_p<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * WgCfg<16>::SLOT);
-        attr = true;
-    }
     WgJobs J{};
     WgFinJobs F{};
     for (int i = 0; i < n; ++i) {
@@ -645,12 +625,15 @@ int launch_p(int n, const fen_wgrad_desc* ds, float* work, hipStream_t s) {
     J.n = n;
     J.nchunk = nchunk;
     J.tpc = tpc;
-    if (cot == 64)
+    if (cot == 64) {
+        fen_detail::opt_in_lds<k_wgrad_p<64>>(2 * WgCfg<64>::SLOT);
         hipLaunchKernelGGL(k_wgrad_p<64>, dim3(n * nchunk, d->Cout / 64, d->Cin / 64), dim3(64 * WgCfg<64>::NW),
                            2 * WgCfg<64>::SLOT, s, *d, J, work);
-    else
+    } else {
+        fen_detail::opt_in_lds<k_wgrad_p<16>>(2 * WgCfg<16>::SLOT);
         hipLaunchKernelGGL(k_wgrad_p<16>, dim3(n * nchunk, 1, d->Cin / 64), dim3(64 * WgCfg<16>::NW),
                            2 * WgCfg<16>::SLOT, s, *d, J, work);
+    }
     FEN_CHECK_LAUNCH();
     const int stride4 = (int)(slab_floats(d) / 4);
     const int nw4 = d->Cout * d->Cin * 9 / 4;   // tap-major: rows co >= cout_valid skipped
@@ -693,17 +676,20 @@ extern "C" int fen_wgrad3x3(const fen_wgrad_desc* d, void* stream) {
     float* part = d->work;
     float* dbpart = d->work + (size_t)nchunk * 9 * d->Cout * d->Cin;
     dim3 grid(nchunk, d->Cout / cot, (d->Cin + 63) / 64);
-    const int npx = d->dtype == FEN_BF16 ? 1 : 2;
-    const int npy = d->dtype == FEN_BF16 ? 1 : (cot * 4 > 128 ? 2 : 1);
-    const size_t lds = (size_t)npx * PANEL_HALO + (size_t)npy * PANEL_TILE;
-    if (d->dtype == FEN_BF16) {
-        if (cot == 64) hipLaunchKernelGGL((k_wgrad<bf16, 64>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
-        else hipLaunchKernelGGL((k_wgrad<bf16, 16>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
-    } else {
-        if (cot == 64) hipLaunchKernelGGL((k_wgrad<float, 64>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
-        else hipLaunchKernelGGL((k_wgrad<float, 16>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
-    }
-    FEN_CHECK_LAUNCH();
+    const int rc = fen_detail::with_dtype(d->dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if constexpr (!std::is_same<T, f16>::value) {   // (check_desc: bf16 or f32)
+            const int npx = sizeof(T) == 2 ? 1 : 2;
+            const int npy = sizeof(T) == 2 ? 1 : (cot * 4 > 128 ? 2 : 1);
+            const size_t lds = (size_t)npx * PANEL_HALO + (size_t)npy * PANEL_TILE;
+            if (cot == 64) hipLaunchKernelGGL((k_wgrad<T, 64>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
+            else hipLaunchKernelGGL((k_wgrad<T, 16>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
+            FEN_CHECK_LAUNCH();
+            return FEN_OK;
+        }
+        return FEN_EINVAL;
+    });
+    if (rc != FEN_OK) return rc;
     const size_t per = (size_t)9 * d->Cout * d->Cin;
     const int nb = (int)((per + 63) / 64);
     hipLaunchKernelGGL(k_wgrad_finalize, dim3(nb), dim3(256), 0, s, nchunk, d->Cout, d->Cin, d->cout_valid,

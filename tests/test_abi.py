@@ -196,3 +196,126 @@ def test_rccl_and_status_entry_points_without_gpu():
     assert lib.fen_status_take(ctypes.addressof(w)) == 3 and w.value == 0
     assert lib.fen_status_take(ctypes.addressof(w)) == 0
     assert lib.fen_status_take(None) == 0
+
+
+def test_unknown_dtype_rejected_by_every_entry_point_without_gpu():
+    """Every exported function that takes a dtype -- a plain `int dtype` or a descriptor's field --
+    answers a code that is no fen_dtype with FEN_EINVAL, given otherwise valid non-null arguments.
+    The refusal precedes any launch (and any read through a pointer), so it runs on CPU."""
+    import ctypes
+    from src.hip import lib as L
+    lib = L.load()
+    P = 0x10000                                                   # never dereferenced
+    win = (ctypes.c_float * 11)(*([1.0 / 11] * 11))               # (the SSIM window is read on the host)
+    winp = ctypes.cast(win, ctypes.c_void_p)
+    jobs = (L.PackJob * 1)()
+    jobs[0].w, jobs[0].out, jobs[0].mode, jobs[0].Cout, jobs[0].Cin = P, P, 0, 64, 64
+    table = ctypes.create_string_buffer(lib.fen_pack_table_bytes(1))
+    total = ctypes.c_size_t(0)
+
+    def descs(dt):
+        c = L.ConvDesc()
+        c.dtype, c.B, c.H, c.W, c.Cin, c.Cout = dt, 1, 16, 16, 64, 64
+        c.x = c.w = c.y = P
+        wg = (L.WgradDesc * 2)()
+        for w in wg:
+            w.dtype, w.B, w.H, w.W, w.Cin, w.Cout, w.cout_valid = dt, 1, 16, 16, 64, 64, 64
+            w.x = w.dy = w.dw = w.work = P
+        r = L.RcabDeferredDesc()
+        r.dtype, r.B, r.H, r.W, r.C, r.Cr = dt, 1, 16, 16, 64, 16
+        r.x = r.w1 = r.w2 = r.b1 = r.b2 = r.alpha = r.t = r.part = P
+        ge = L.RcabDeferredDesc()
+        ge.dtype, ge.B, ge.H, ge.W, ge.C, ge.Cr = dt, 1, 16, 16, 64, 16
+        ge.x = ge.tp = ge.pp = ge.pfc1 = ge.pfc2 = P
+        rb = L.RcabBwdDesc()
+        rb.dtype, rb.B, rb.H, rb.W, rb.C = dt, 1, 16, 16, 64
+        rb.dt = rb.w2t = rb.w1t = rb.z1 = rb.alpha = rb.dz1 = rb.dalpha_part = rb.dx = rb.dy = P
+        gs = (L.GroupStripDesc * 2)()
+        nbytes = lib.fen_group_strip_chain_work_bytes(1, 64, 2)
+        for g, d in enumerate(gs):
+            d.dtype, d.B, d.H, d.W, d.C, d.Cr, d.nb, d.res_scale = dt, 1, 64, 64, 64, 16, 1, 0.2
+            d.x, d.y = P * (g + 1), P * (g + 2)
+            d.w1[0] = d.b1[0] = d.alpha[0] = d.w2[0] = d.b2[0] = d.fc1[0] = d.fc2[0] = P
+            d.wg = d.bg = P
+            d.work, d.work_bytes = 0x100000, nbytes
+        gb = L.GroupStripBwdDesc()
+        gb.dtype, gb.B, gb.H, gb.W, gb.C, gb.Cr, gb.nb, gb.res_scale = dt, 1, 64, 64, 64, 16, 1, 0.2
+        gb.dy, gb.dx, gb.wgt, gb.work = P, 2 * P, P, 0x100000
+        gb.work_bytes = lib.fen_group_strip_bwd_work_bytes(1, 64)
+        for f in ("w1t", "w2t", "alpha", "fc1", "fc2", "z1", "t", "s", "mean", "hid", "dt", "dz1", "dalpha_part",
+                  "dw1p", "dw2p", "a1"):
+            getattr(gb, f)[0] = P
+        c128 = L.RcabC128Desc()
+        c128.dtype, c128.B, c128.H, c128.W, c128.C, c128.Cr, c128.mode = dt, 1, 16, 16, 128, 16, 3
+        c128.x, c128.w, c128.bias, c128.res, c128.y = P, P, P, P, 2 * P
+        rc = L.RrdbConvDesc()
+        rc.dtype, rc.B, rc.H, rc.W, rc.Cin, rc.Cout = dt, 1, 8, 8, 64, 32
+        rc.x, rc.w, rc.bias, rc.y, rc.x_stride, rc.y_stride, rc.y_off = P, P, P, 2 * P, 192, 192, 64
+        blk = L.RrdbBlockDesc()
+        blk.dtype, blk.B, blk.H, blk.W, blk.num_feat, blk.num_grow_ch = dt, 1, 8, 8, 64, 32
+        blk.buf, blk.next = P, 2 * P
+        for k in range(5):
+            blk.w[k] = blk.bias[k] = P
+        return c, wg, r, ge, rb, gs, gb, c128, rc, blk
+
+    for dt in (3, -1):
+        c, wg, r, ge, rb, gs, gb, c128, rc, blk = descs(dt)
+        calls = {
+            "fen_conv3x3": lambda: lib.fen_conv3x3(c, None),
+            "fen_wgrad3x3": lambda: lib.fen_wgrad3x3(wg[0], None),
+            "fen_wgrad3x3_multi": lambda: lib.fen_wgrad3x3_multi(2, ctypes.cast(wg, ctypes.c_void_p), None),
+            "fen_rcab_deferred": lambda: lib.fen_rcab_deferred(r, None),
+            "fen_rcab_group_end": lambda: lib.fen_rcab_group_end(ge, P, P, P, P, None),
+            "fen_rcab_bwd": lambda: lib.fen_rcab_bwd(rb, None),
+            "fen_group_strip": lambda: lib.fen_group_strip(gs[0], None),
+            "fen_group_strip_chain_prepare": lambda: lib.fen_group_strip_chain_prepare(gs, 2, None, None),
+            "fen_group_strip_chain": lambda: lib.fen_group_strip_chain(gs, 2, None, None),
+            "fen_group_strip_bwd": lambda: lib.fen_group_strip_bwd(gb, None),
+            "fen_rcab_c128": lambda: lib.fen_rcab_c128(c128, None),
+            "fen_rrdb_conv": lambda: lib.fen_rrdb_conv(rc, None),
+            "fen_rrdb_block": lambda: lib.fen_rrdb_block(blk, None),
+            "fen_rrdb_first": lambda: lib.fen_rrdb_first(dt, 1, 3, 16, 16, P, P, P, P, 192, None, None),
+            "fen_conv_first_fwd": lambda: lib.fen_conv_first_fwd(dt, 1, 3, 16, 16, 64, P, P, P, P, None),
+            "fen_conv_first_fwd_ex": lambda: lib.fen_conv_first_fwd_ex(dt, 1, 3, 16, 16, 64, P, P, P, P, P, 0.2, P, None),
+            "fen_conv_first_wgrad": lambda: lib.fen_conv_first_wgrad(dt, 1, 3, 16, 16, 64, P, P, P, P, 0, P, None),
+            "fen_conv_last_dgrad": lambda: lib.fen_conv_last_dgrad(dt, 1, 16, 16, 64, 3, P, P, P, P, P, P, P, None),
+            "fen_conv_last_bwd": lambda: lib.fen_conv_last_bwd(dt, 1, 16, 16, 64, 3, P, P, P, P, P, P, P, P, P, None),
+            "fen_se_fused": lambda: lib.fen_se_fused(dt, 1, 256, 64, 16, 4, 1 / 256, P, P, P, P, P, P, P, 0.2, P, P, None),
+            "fen_se_apply": lambda: lib.fen_se_apply(dt, 1, 256, 64, P, P, 0.2, P, P, None),
+            "fen_pool_dot": lambda: lib.fen_pool_dot(dt, 1, 256, 64, P, P, P, None),
+            "fen_se_bwd_fused": lambda: lib.fen_se_bwd_fused(dt, 1, 256, 64, 16, 4, 1 / 256, 0.2, P, P, P, P, P, P, P, P,
+                                                             P, P, P, None),
+            "fen_se_bwd_apply": lambda: lib.fen_se_bwd_apply(dt, 1, 256, 64, P, P, 0.2, P, P, None),
+            "fen_pack_conv_w": lambda: lib.fen_pack_conv_w(dt, 0, 64, 64, P, P, None),
+            "fen_pack_table": lambda: lib.fen_pack_table(dt, 1, ctypes.cast(jobs, ctypes.c_void_p),
+                                                         ctypes.cast(table, ctypes.c_void_p), ctypes.byref(total)),
+            "fen_pack_multi": lambda: lib.fen_pack_multi(dt, 1, P, 256, None),
+            "fen_nchw_to_nhwc": lambda: lib.fen_nchw_to_nhwc(dt, 1, 3, 16, 16, 8, P, P, None),
+            "fen_nhwc_to_nchw": lambda: lib.fen_nhwc_to_nchw(dt, 1, 3, 16, 16, P, P, None),
+            "fen_prelu_bwd_unshuffle": lambda: lib.fen_prelu_bwd_unshuffle(dt, 1, 16, 16, 64, P, P, P, P, P, None),
+            "fen_maxpool2": lambda: lib.fen_maxpool2(dt, 1, 16, 16, 64, P, P, None),
+            "fen_maxpool2_bwd_relu": lambda: lib.fen_maxpool2_bwd_relu(dt, 1, 16, 16, 64, P, P, P, None),
+            "fen_feat_loss": lambda: lib.fen_feat_loss(dt, 64, P, 0, 1.0, P, 0, P, None),
+            "fen_ssim": lambda: lib.fen_ssim(dt, 1, 3, 16, 16, P, P, winp, 11, 1e-4, 9e-4, P, P, 1.0, 2, None),
+            "fen_ssim_ex": lambda: lib.fen_ssim_ex(dt, 1, 3, 16, 16, P, P, winp, 11, 1e-4, 9e-4, P, P, 1.0, 2, P, None),
+            "fen_msssim": lambda: lib.fen_msssim(dt, 1, 3, 32, 32, P, P, winp, 11, 1e-4, 9e-4, P, 2, P, P, P, 1.0, 1, None),
+            "fen_bn_stats": lambda: lib.fen_bn_stats(dt, 64, 64, P, 1e-5, 0.1, P, None, None, P, None),
+            "fen_bn_stats_n": lambda: lib.fen_bn_stats_n(dt, 2, 64, 64, P, 1e-5, 0.1, P, None, None, P, None),
+            "fen_bn_apply": lambda: lib.fen_bn_apply(dt, 64, 64, P, P, P, P, P, 0.2, P, None),
+            "fen_bn_apply_n": lambda: lib.fen_bn_apply_n(dt, 2, 64, 64, P, P, P, 64, P, P, 0.2, P, None),
+            "fen_bn_bwd": lambda: lib.fen_bn_bwd(dt, 64, 64, P, P, P, P, P, 0.2, P, P, P, 0, P, None),
+            "fen_bn_bwd_n": lambda: lib.fen_bn_bwd_n(dt, 2, 64, 64, P, P, P, P, P, 0.2, P, P, P, 0, P, None),
+            "fen_subsample2": lambda: lib.fen_subsample2(dt, 1, 16, 16, 64, P, P, None),
+            "fen_s2d2": lambda: lib.fen_s2d2(dt, 1, 16, 16, 64, P, P, 0, None),
+            "fen_zero_insert2": lambda: lib.fen_zero_insert2(dt, 1, 8, 8, 64, P, P, None),
+        }
+        got = {name: call() for name, call in calls.items()}
+        wrong = {name: rc_ for name, rc_ in got.items() if rc_ != -1}
+        assert not wrong, (dt, wrong)
+    # the list is the header's: every status-returning function with a dtype parameter or descriptor
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fen.h")).read(), flags=re.S)
+    takes = set(re.findall(r"\bint (fen_[a-z0-9_]+)\s*\(\s*(?:int dtype|const fen_(?:conv|wgrad|rcab_deferred|"
+                           r"group_strip|rcab_c128|group_strip_bwd|rcab_bwd|rrdb_conv|rrdb_block)_desc\*)", hdr))
+    takes -= {n for n in takes if n.endswith("_supported")}      # 0 / 1 queries, not statuses
+    takes.add("fen_wgrad3x3_multi")                               # (int n, const fen_wgrad_desc* ds, ...)
+    assert takes == set(calls), takes ^ set(calls)

@@ -51,22 +51,18 @@ nw = int((a[0, :, 0, 0] != 0).sum())
 a = a[:, :nw]
 rt = a[..., 0]
 t0 = rt[:, :, 0].min()
-# slot -> label: 0 start, 1 end of start-up, 2+3k / 3+3k / 4+3k: tile k after MFMAs / after
-# epilogue / after the closing barrier; 13, 14: q-kernel start-up (DMA issued, DMA landed)
+# slot -> label: 0 start, 1 end of start-up, 2+2k / 3+2k: phase k after its work / after its
+# closing barrier
 labels = {0: "start", 1: "startup"}
-if os.environ.get("FEN_CONV_VARIANT", "0") == "5":   # single-group kernel: 3 stamps per tile
-    for k in range(4):
-        labels.update({2 + 3 * k: f"t{k}_mfma", 3 + 3 * k: f"t{k}_epi", 4 + 3 * k: f"t{k}_bar"})
-else:                                                # ping-pong kernel: 2 stamps per phase
-    for k in range(7):
-        labels.update({2 + 2 * k: f"ph{k}_work", 3 + 2 * k: f"ph{k}_bar"})
+for k in range(7):                                   # ping-pong kernel: 2 stamps per phase
+    labels.update({2 + 2 * k: f"ph{k}_work", 3 + 2 * k: f"ph{k}_bar"})
 out = {"blocks": int(used.sum()), "waves": nw}
 for i in sorted(labels):
     valid = (rt[:, :, i] != 0).all(axis=1)
     if not valid.any():
         continue
     r = (rt[valid, :, i] - t0) / 100.0          # us since the first start, per wave
-    if os.environ.get("FEN_CONV_VARIANT", "0") == "5" or nw < 8:
+    if nw < 8:
         out[labels[i]] = [round(float(np.median(r.min(1))), 2), round(float(np.median(r.max(1))), 2)]
     else:   # [group A min, max, group B min, max]
         out[labels[i]] = [round(float(np.median(r[:, :4].min(1))), 2), round(float(np.median(r[:, :4].max(1))), 2),
