@@ -11,15 +11,27 @@ training precision) each is compared to the fp32 oracle and the strip path must 
 from it than the per-RCAB path (x 1.25, + a floor of 1e-2 rel-L2 for tensors both get almost
 exactly), whole-tensor rel-L2 for dx and for every parameter gradient; in fp16 (data path and
 PReLU / SE gradients only: the weight-gradient kernels are bf16 / fp32) at absolute bounds, dx
-5e-3 and those gradients 2e-2.  A wrong halo row, hand-off, tap, gate or SE term shows up as O(1).
+5e-3 and those gradients 2e-2.  These whole-tensor numbers see a fault that repeats in every
+image (a wrong tap, gate or SE term: O(1)); a wrong halo row or hand-off in ONE image is diluted
+by sqrt(faulty rows / (B * H)), and one lost strip's part of a weight gradient is 1 / (B * S) of
+the sum.  dx is therefore also bounded per (image, row / column / channel) band and per element
+by a fixed factor of the CPU yardstick's error (parity.assert_local: autograd of the oracle with
+the gradients rounded where the kernels round them); test_gpu_strip_local.py lights one strip
+at a time so that every gradient comes from that strip alone.
 Shapes: the bench's (B=32, 64x64, 10 RCABs), a single strip per image (H=8), three strips
 (H=24), 16 strips (H=128), more strips than CUs (B=40: 320 blocks), with the second residual
 (the body's first group).  Every launch leaves its counters at zero and its error word clear;
 repeats and graph replays are bit-identical."""
+import os
+import sys
+
 import pytest
 import torch
 
 from oracle import fen_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import parity  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -99,6 +111,11 @@ def _oracle(q, n, x_nchw, dy_nchw, dtype, dres_nchw=None):
     return dx, {k: v.grad for k, v in leaves.items()}
 
 
+def _rounded(q, dtype):
+    """The parameters as _oracle sees them: conv weights rounded to the 16-bit format."""
+    return {k: (v.to(dtype).float() if v.dim() == 4 else v) for k, v in q.items()}
+
+
 def _work_error(ctx):
     from src.hip import lib as L
     L.check_strip_status()
@@ -139,6 +156,8 @@ def test_group_strip_bwd_vs_oracle(B, H, n, dres):
     es, ep = _rel(nchw(dx_s), dx_ref), _rel(nchw(dx_p), dx_ref)
     print(f"{prec} B={B} H={H} n={n} dres={dres}: dx strip {es:.2e} per-RCAB {ep:.2e}")
     assert es <= 1.25 * ep + floor, (es, ep)
+    dx_yard, _ = parity.rounded_group_grads(x, _rounded(q, dtype), n, dtype, dy, r)
+    parity.assert_local(nchw(dx_s), dx_ref, dx_yard, f"dx {prec} B={B} H={H} n={n}")
     worst = (0.0, "")
     for k in g_ref:
         es, ep = _rel(g_s[k], g_ref[k]), _rel(g_p[k], g_ref[k])
@@ -172,6 +191,8 @@ def test_group_strip_bwd_fp16_vs_oracle(B, H, n, dres):
     print(f"fp16 B={B} H={H} n={n} dres={dres}: dx {e:.2e}, worst PReLU/SE gradient {worst[1]} {worst[0]:.2e}")
     assert e <= 5e-3
     assert worst[0] <= 2e-2, worst
+    dx_yard, _ = parity.rounded_group_grads(x, _rounded(q, dtype), n, dtype, dy, r)
+    parity.assert_local(dx_s.float().cpu().permute(0, 3, 1, 2), dx_ref, dx_yard, f"dx fp16 B={B} H={H} n={n}")
 
 
 def test_group_strip_bwd_vs_per_rcab_bench_shape():
