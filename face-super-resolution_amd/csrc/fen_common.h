@@ -203,6 +203,30 @@ __device__ __forceinline__ float group16_sum(float v) {
     return v;
 }
 
+// group16_sum of N independent values, one DPP step at a time over all of them: a step reads
+// what the step before wrote N instructions earlier, not the previous instruction's result (the
+// DPP read-after-write hazard costs wait states).  Per value the same tree, the same bits.
+template <int N>
+__device__ __forceinline__ void group16_sum_n(float (&v)[N]) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += dpp_f<0xB1>(v[k]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += dpp_f<0x4E>(v[k]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += dpp_f<0x141>(v[k]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += dpp_f<0x140>(v[k]);
+    __builtin_amdgcn_sched_barrier(0);
+    // opaque results: a vector store of them must not seed a vectorisation of the adds above
+    // (packed adds cannot take a DPP operand: every step would become a v_mov_dpp and a v_pk_add)
+#pragma unroll
+    for (int k = 0; k < N; ++k) asm volatile("" : "+v"(v[k]));
+}
+
 // Keys cubic convolution, A = -0.75 (torch upsample_bicubic2d coefficients)
 __device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
     const float A = -0.75f;

@@ -446,10 +446,8 @@ __global__ __launch_bounds__(512, 1) void k_group_strip(const GsArgs A) {
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     __builtin_amdgcn_sched_barrier(0);
-                    const float x0 = lo16<T>(xr[m][p].x), x1 = hi16<T>(xr[m][p].x);
-                    const float x2 = lo16<T>(xr[m][p].y), x3 = hi16<T>(xr[m][p].y);
-                    xr[m][p] = pk4<T>(lo16<T>(tr[m][p].x) * gt[m][0] + x0, hi16<T>(tr[m][p].x) * gt[m][1] + x1,
-                                      lo16<T>(tr[m][p].y) * gt[m][2] + x2, hi16<T>(tr[m][p].y) * gt[m][3] + x3);
+                    xr[m][p] = make_uint2(fma2_16<T>(tr[m][p].x, gt[m][0], gt[m][1], xr[m][p].x),
+                                          fma2_16<T>(tr[m][p].y, gt[m][2], gt[m][3], xr[m][p].y));
                 }
         }
         if (j > 0 || g > 0) write_row_lds(wave + 1, xr);    // (a chained group's x_0: the previous output)
@@ -507,14 +505,9 @@ __global__ __launch_bounds__(512, 1) void k_group_strip(const GsArgs A) {
             const float g8[8] = {ga.x, ga.y, ga.z, ga.w, gb.x, gb.y, gb.z, gb.w};
             char* hb = img + (hs == 0 ? 0 : SR + 1) * IROW + hcol((lane >> 3) + 1, lane & 7) + hk0 * 1024;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float xf[8], tf[8], yv[8];
-                unpack16<T>(nx[k], xf);
-                unpack16<T>(nt[k], tf);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) yv[e] = tf[e] * g8[e] + xf[e];
-                *(uint4*)(hb + k * 1024) = pack16<T>(yv);
-            }
+            for (int k = 0; k < 4; ++k)
+                *(uint4*)(hb + k * 1024) = make_uint4(fma2_16<T>(nt[k].x, g8[0], g8[1], nx[k].x), fma2_16<T>(nt[k].y, g8[2], g8[3], nx[k].y),
+                                                      fma2_16<T>(nt[k].z, g8[4], g8[5], nx[k].z), fma2_16<T>(nt[k].w, g8[6], g8[7], nx[k].w));
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         } else if (MULTI && j == 0 && g > 0 && hwave) {
             char* hb = img + (hs == 0 ? 0 : SR + 1) * IROW + hcol((lane >> 3) + 1, lane & 7) + hk0 * 1024;
@@ -609,26 +602,64 @@ __global__ __launch_bounds__(512, 1) void k_group_strip(const GsArgs A) {
         // while its SIMD partner still issues MFMAs, instead of idling at B_E (GS_LATE_EPI: after)
         uint2 av[4][4];
         auto a1_epilogue = [&]() {
+#ifdef GS_PLAIN_EPI   // A/B variant: the plain form everywhere
+            constexpr bool plain = true;
+#else
+            constexpr bool plain = SAVE;
+#endif
+            if constexpr (plain) {
+                // training: the plain form.  The accumulators stay live past the epilogue (z1),
+                // and the 2-vector / interleaved form below costs the registers that are left:
+                // it spilled to scratch inside the RCAB loop (bf16: 20-56 B per lane)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float4 bb = *(const float4*)(cst + 16 * m + 4 * q);
-                const float4 aa = *(const float4*)(cst + 64 + 16 * m + 4 * q);
-                const float bia[4] = {bb.x, bb.y, bb.z, bb.w}, alp[4] = {aa.x, aa.y, aa.z, aa.w};
-                float rs[4] = {0.f, 0.f, 0.f, 0.f};
+                for (int m = 0; m < 4; ++m) {
+                    const float4 bb = *(const float4*)(cst + 16 * m + 4 * q);
+                    const float4 aa = *(const float4*)(cst + 64 + 16 * m + 4 * q);
+                    const float bia[4] = {bb.x, bb.y, bb.z, bb.w}, alp[4] = {aa.x, aa.y, aa.z, aa.w};
+                    float rs[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    float v[4];
+                    for (int p = 0; p < 4; ++p) {
+                        float v[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = prelu_f(acc[m][p][i] + bia[i], alp[i]);
-                    av[m][p] = pk4<T>(v[0], v[1], v[2], v[3]);
+                        for (int i = 0; i < 4; ++i) v[i] = prelu_f(acc[m][p][i] + bia[i], alp[i]);
+                        av[m][p] = pk4<T>(v[0], v[1], v[2], v[3]);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) rs[i] += v[i];
+                        for (int i = 0; i < 4; ++i) rs[i] += v[i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float s = group16_sum(rs[i]);
+                        if (c16 == 0) red[wave * 64 + 16 * m + 4 * q + i] = s;
+                    }
                 }
+            } else {
+                // inference: bias adds and row sums as 2-vectors (v_pk_add_f32); the 16 row-sum
+                // reductions issued step by step across all 16 values, so a DPP step never reads a
+                // register written by the instruction before it (no hazard stalls) -- each value's
+                // tree is group16_sum's, the sums in the same order: the same bits
+                float sv[16];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float s = group16_sum(rs[i]);
-                    if (c16 == 0) red[wave * 64 + 16 * m + 4 * q + i] = s;
+                for (int m = 0; m < 4; ++m) {
+                    const float4 bb = *(const float4*)(cst + 16 * m + 4 * q);
+                    const float4 aa = *(const float4*)(cst + 64 + 16 * m + 4 * q);
+                    const f32x2 b01 = {bb.x, bb.y}, b23 = {bb.z, bb.w};
+                    const float alp[4] = {aa.x, aa.y, aa.z, aa.w};
+                    f32x2 r01 = {0.f, 0.f}, r23 = {0.f, 0.f};
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const f32x2 z01 = f32x2{acc[m][p][0], acc[m][p][1]} + b01, z23 = f32x2{acc[m][p][2], acc[m][p][3]} + b23;
+                        const f32x2 v01 = {prelu_f(z01.x, alp[0]), prelu_f(z01.y, alp[1])};
+                        const f32x2 v23 = {prelu_f(z23.x, alp[2]), prelu_f(z23.y, alp[3])};
+                        av[m][p] = pk4<T>(v01.x, v01.y, v23.x, v23.y);
+                        r01 += v01;
+                        r23 += v23;
+                    }
+                    sv[4 * m] = r01.x, sv[4 * m + 1] = r01.y, sv[4 * m + 2] = r23.x, sv[4 * m + 3] = r23.y;
                 }
+                group16_sum_n(sv);
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (c16 == 0) red[wave * 64 + 16 * (k >> 2) + 4 * q + (k & 3)] = sv[k];
             }
         };
 #ifndef GS_LATE_EPI

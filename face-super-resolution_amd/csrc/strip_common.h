@@ -25,6 +25,28 @@ __device__ __forceinline__ uint2 pk4(float a, float b, float c, float d) {
     return make_uint2(pack2<T>(a, b), pack2<T>(c, d));
 }
 
+// the combine x + g * t on one 16-bit pair (t and x as stored, the gates fp32): per element one
+// fp32 FMA and one rounding to T.  fp16: v_fma_mix_f32 (f16 sources t and x by op_sel_hi, widened
+// exactly; the gate fp32; an fp32 FMA -- the bits of convert, fmaf) and the packed conversion:
+// 3 instructions per pair instead of 4 conversions + 1 packed FMA + 1 packed conversion.
+// Inline asm: in plain C++ the two FMAs are vectorised to v_pk_fma_f32 before instruction
+// selection could fold the conversions.  (v_fma_mixlo/hi_f16, which would also round to f16,
+// is NOT used: on gfx950 its result differs in the last bit from fmaf then convert -- measured,
+// tests/test_gpu_strip_golden.py.)  bf16: shifts, a packed FMA and the packed conversion.
+template <typename T>
+__device__ __forceinline__ unsigned fma2_16(unsigned t, float g0, float g1, unsigned x) {
+    return pack2<T>(lo16<T>(t) * g0 + lo16<T>(x), hi16<T>(t) * g1 + hi16<T>(x));
+}
+#ifndef GS_NO_MIX   // (A/B variant: the fp16 combine through the generic form)
+template <>
+__device__ __forceinline__ unsigned fma2_16<f16>(unsigned t, float g0, float g1, unsigned x) {
+    float lo, hi;
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(lo) : "v"(t), "v"(g0), "v"(x));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(hi) : "v"(t), "v"(g1), "v"(x));
+    return pack2<f16>(lo, hi);
+}
+#endif
+
 // lanes q and q^1 (same pixel: rows 2k, 2k+1 of 16 lanes) trade one 4-channel half so each
 // holds 8 consecutive channels: lo = the lane's channels of m-block 2mp, hi = of m-block
 // 2mp + 1; the result is chunk chunk_of(mp, q) of the pixel.  v_permlane16_swap swaps the odd
