@@ -135,7 +135,8 @@ def test_conv_dot_epilogue(dtype, B, H, W, nres):
 @pytest.mark.parametrize("B,H,W", [(2, 16, 32), (2, 16, 64), (1, 24, 128)])
 def test_upsample_conv_shuffle_prelu(dtype, B, H, W):
     """The upsampler stage conv (64 -> 256 + bias + PixelShuffle + PReLU, y_pre kept), partial
-    and full tile rows, several tiles per block."""
+    and full tile rows.  4, 8 and 16 tiles on 64 slots (one block per CU, four co-blocks per
+    tile): one tile per block -- several tiles per block are test_gpu_conv_local.py's."""
     from src.hip import lib as L, net
     torch.manual_seed(2)
     C = 64
