@@ -1523,6 +1523,21 @@ int conv_dispatch(const fen_conv_desc* d, hipStream_t s) {
     const bool small = (size_t)d->B * d->H * d->W * 128 < (size_t)0x7fff0000;
     const bool s2d = d->s2d_in > 0 || d->s2d_out > 0;
     const bool persist = H16 && d->Cin == 64 && small && !(epi & FEN_EPI_UNSHUFFLE) && !s2d;
+    if (epi & FEN_EPI_NOSKIP) {
+        // conv_last without skip or clamp: the streaming kernel, else the RRDB path's NCHW conv
+        if (!(epi & FEN_EPI_LAST) || d->Cout > 4 || d->lr || d->scale || d->clamp) return FEN_EINVAL;
+        if (epi & ~(FEN_EPI_LAST | FEN_EPI_NOSKIP | FEN_EPI_BIAS)) return FEN_EUNSUPPORTED;
+        if (fen_detail::conv_last_noskip_fast_ok(d)) return fen_detail::launch_conv_last(d, s);
+        if (!d->y) return FEN_EINVAL;
+        if (d->hr || !(epi & FEN_EPI_BIAS) || d->debug) return FEN_EUNSUPPORTED;
+        fen_rrdb_conv_desc c = {};
+        c.dtype = d->dtype;
+        c.B = d->B; c.H = d->H; c.W = d->W; c.Cin = d->Cin; c.Cout = d->Cout;
+        c.x = d->x; c.x_stride = d->Cin;
+        c.w = d->w; c.bias = d->bias;
+        c.y = d->y; c.nchw_out = 1;
+        return fen_rrdb_conv(&c, s);
+    }
     if (epi & FEN_EPI_LAST) {
         if (d->Cout > 4 || !d->lr || d->scale <= 0 || d->H % d->scale || d->W % d->scale) return FEN_EINVAL;
         if (epi & ~(FEN_EPI_LAST | FEN_EPI_BIAS)) return FEN_EUNSUPPORTED;
@@ -1611,7 +1626,7 @@ extern "C" int fen_conv3x3(const fen_conv_desc* d, void* stream) {
     if ((epi & FEN_EPI_BIAS) && !d->bias) return FEN_EINVAL;
     if ((epi & (FEN_EPI_PRELU | FEN_EPI_PRELU_BWD)) && !d->alpha) return FEN_EINVAL;
     if ((epi & (FEN_EPI_PRELU_BWD | FEN_EPI_DOT | FEN_EPI_RELU_BWD)) && !d->pre_in) return FEN_EINVAL;
-    if (epi & ~0x10ff) return FEN_EINVAL;
+    if (epi & ~0x30ff) return FEN_EINVAL;
     if ((epi & FEN_EPI_RELU_BWD) &&
         (epi & (FEN_EPI_PRELU_BWD | FEN_EPI_DOT | FEN_EPI_LAST | FEN_EPI_SHUFFLE | FEN_EPI_UNSHUFFLE)))
         return FEN_EUNSUPPORTED;

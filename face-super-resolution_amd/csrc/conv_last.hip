@@ -21,6 +21,11 @@
 //     operation order as bicubic_sample (fen_common.h);
 //   * the tile's loss sum is combined over the 8 waves through LDS and written one
 //     iteration later (no extra barrier).
+//
+// SKIP = false (FEN_EPI_LAST | FEN_EPI_NOSKIP, the transfer model's conv_last, transfer.py:77):
+//   sr = conv3x3(a, w_last) + b_last, no bicubic skip and no clamp -- the same staging, store and
+//   L1 epilogue; loader 0 issues no LR patch pieces (its vmcnt budget shrinks by those 4) and the
+//   compute waves skip both bicubic passes.
 #include "fen_common.h"
 
 namespace {
@@ -42,7 +47,7 @@ constexpr int PIECES1 = HALO_DMA / 2;           // loader 1: odd halo pieces (+ 
 static_assert(CL_LDS <= 163840, "LDS budget");
 static_assert(2 * PIECES0 <= 63 && 2 * (PIECES1 + 4) <= 63, "vmcnt field");
 
-template <typename T, bool TRAIN>
+template <typename T, bool TRAIN, bool SKIP>
 __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc d) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
@@ -65,7 +70,7 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
     //      pieces back to back, so the per-piece cost is an add for interior tiles)
     const int lw = wave - LW;                     // 0, 1 on the loader waves
     const i32x4 xr = make_rsrc(d.x, (unsigned)((size_t)B * H * W * 128));
-    const i32x4 lrr = make_rsrc(d.lr, (unsigned)((size_t)B * Cout * Hs * Ws * 4));
+    const i32x4 lrr = make_rsrc(SKIP ? d.lr : nullptr, SKIP ? (unsigned)((size_t)B * Cout * Hs * Ws * 4) : 0u);
     const i32x4 hrr = make_rsrc(train ? d.hr : d.lr, train ? (unsigned)((size_t)B * Cout * H * W * 4) : 0u);
     constexpr int PPW = (HALO_DMA + 1) / 2;
     int rel[PPW], hrc[PPW];
@@ -105,6 +110,7 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
             }
         }
         if (lw == 0) {
+            if constexpr (SKIP) {
             // LR patch rows h0/4-2.., cols w0/4-2.. of channel ch: lane = row * 8 + col
             const int gy = min(max((h0 >> 2) - 2 + (lane >> 3), 0), Hs - 1);
             const int gx = min(max((w0 >> 2) - 2 + (lane & 7), 0), Ws - 1);
@@ -113,6 +119,7 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
             for (int ch = 0; ch < 4; ++ch) {
                 const int voff = ch < Cout ? (((b * Cout + ch) * Hs + gy) * Ws + gx) * 4 : 0x7ffffff0;
                 dma4(lrr, __builtin_amdgcn_readfirstlane(lslot + ch * 256), voff);
+            }
             }
         } else if (train) {
             // target rows h0.., 16 floats each: lane = row * 4 + 16-B chunk
@@ -148,7 +155,7 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
     for (int i = 0; i < nmine; ++i) {
         if (lw >= 0) {                            // this tile landed (the next may stay in flight)
             if (i + 1 < nmine) {
-                if (lw == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES0) : "memory");
+                if (lw == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SKIP ? PIECES0 : PIECES0 - 4) : "memory");
                 else if (train) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES1 + 4) : "memory");
                 else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES1) : "memory");
             } else {
@@ -207,11 +214,13 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
         const int pr0 = (wave * RPW) >> 2;        // patch row of LR row a - 2
         const float* lrp = (const float*)(smem + O_LR + sl * 1024) + (q * LR_P + pr0) * LR_P + relc;
         const int ph = (wave * RPW) & 3;          // m % 4 of this wave's first row
-        float hrow[4];
+        float hrow[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (SKIP) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* row = lrp + (r + (ph >= 2 ? 1 : 0)) * LR_P;
-            hrow[r] = row[0] * cx[0] + row[1] * cx[1] + row[2] * cx[2] + row[3] * cx[3];
+            for (int r = 0; r < 4; ++r) {
+                const float* row = lrp + (r + (ph >= 2 ? 1 : 0)) * LR_P;
+                hrow[r] = row[0] * cx[0] + row[1] * cx[1] + row[2] * cx[2] + row[3] * cx[3];
+            }
         }
         const float* hrp = (const float*)(smem + O_HR + sl * 4096) + (wave * RPW) * 16 + c16;
         float lsum = 0.f;
@@ -225,8 +234,10 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
             float cy[4];
             cubic_coeffs(sy - fy, cy);
             float bic = 0.f;
+            if constexpr (SKIP) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) bic += hrow[k] * cy[k];
+                for (int k = 0; k < 4; ++k) bic += hrow[k] * cy[k];
+            }
             // conv value of channel q: lane (0, c16) holds co 0..3 of pixel c16 (acc[n][r], co =
             // 4q + r); every lane takes its channel's from there -- one 48-lane store per row
             // instead of exec-masked 16-lane stores per channel
@@ -237,7 +248,7 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
                 cq = q == r ? t : cq;
             }
             float v = cq + bias_q + bic;
-            if (d.clamp) v = fminf(fmaxf(v, 0.f), 1.f);
+            if (SKIP && d.clamp) v = fminf(fmaxf(v, 0.f), 1.f);
             if (d.y && chq) ((float*)d.y)[(((size_t)b * Cout + q) * H + h) * W + w0 + c16] = v;
             if (train) {
                 const float diff = chq ? v - hrp[q * 256 + n * 16] : 0.f;
@@ -274,23 +285,36 @@ __global__ __launch_bounds__(CL_THREADS, 1) void k_conv_last(const fen_conv_desc
 
 namespace fen_detail {
 
-bool conv_last_fast_ok(const fen_conv_desc* d) {
-    return (d->dtype == FEN_BF16 || d->dtype == FEN_F16) && d->Cin == 64 && d->Cout <= 4 && d->scale == 4 && d->H % 16 == 0 &&
+// the kernel's envelope but for the skip's scale
+static bool conv_last_shape_ok(const fen_conv_desc* d) {
+    return (d->dtype == FEN_BF16 || d->dtype == FEN_F16) && d->Cin == 64 && d->Cout <= 4 && d->H % 16 == 0 &&
            d->W % 16 == 0 && d->H <= 8192 && d->W <= 8192 && d->debug == 0 &&
            (size_t)d->B * d->H * d->W * 128 < (size_t)0x7fff0000;
 }
+
+bool conv_last_fast_ok(const fen_conv_desc* d) { return d->scale == 4 && conv_last_shape_ok(d); }
+
+bool conv_last_noskip_fast_ok(const fen_conv_desc* d) { return conv_last_shape_ok(d); }
 
 int launch_conv_last(const fen_conv_desc* d, hipStream_t s) {
     const int ntiles = d->B * (d->H >> 4) * (d->W >> 4);
     const int grid = persistent_grid(ntiles, 1);
     return with_dtype16(d->dtype, [&](auto tag) -> int {
         using T = decltype(tag);
-        if (d->hr) {
-            opt_in_lds<k_conv_last<T, true>>(CL_LDS);
-            hipLaunchKernelGGL((k_conv_last<T, true>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
+        if (d->epi & FEN_EPI_NOSKIP) {
+            if (d->hr) {
+                opt_in_lds<k_conv_last<T, true, false>>(CL_LDS);
+                hipLaunchKernelGGL((k_conv_last<T, true, false>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
+            } else {
+                opt_in_lds<k_conv_last<T, false, false>>(CL_LDS);
+                hipLaunchKernelGGL((k_conv_last<T, false, false>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
+            }
+        } else if (d->hr) {
+            opt_in_lds<k_conv_last<T, true, true>>(CL_LDS);
+            hipLaunchKernelGGL((k_conv_last<T, true, true>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
         } else {
-            opt_in_lds<k_conv_last<T, false>>(CL_LDS);
-            hipLaunchKernelGGL((k_conv_last<T, false>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
+            opt_in_lds<k_conv_last<T, false, true>>(CL_LDS);
+            hipLaunchKernelGGL((k_conv_last<T, false, true>), dim3(grid), dim3(CL_THREADS), CL_LDS, s, *d);
         }
         FEN_CHECK_LAUNCH();
         return FEN_OK;

@@ -416,5 +416,7 @@ void opt_in_lds(int bytes) {
 // conv_last fast path (conv_last.hip): bf16, Cin 64, Cout <= 4, x4 skip, H and W multiples of 16
 namespace fen_detail {
 bool conv_last_fast_ok(const fen_conv_desc* d);
+// ... without the skip (FEN_EPI_NOSKIP): the same envelope, no scale
+bool conv_last_noskip_fast_ok(const fen_conv_desc* d);
 int launch_conv_last(const fen_conv_desc* d, hipStream_t s);
 }  // namespace fen_detail

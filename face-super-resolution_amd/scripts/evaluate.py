@@ -2,7 +2,7 @@
 """Evaluate a checkpoint: per-image PSNR / SSIM over a validation set on the HIP path.
 
     python scripts/evaluate.py --checkpoint X.pth [--data-root DIR | --synthetic N] \\
-        [--batch-size 32] [--precision fp16|bf16|fp32] [--quantize] [--json OUT] [--model custom|esrgan]
+        [--batch-size 32] [--precision fp16|bf16|fp32] [--quantize] [--json OUT] [--model custom|esrgan|transfer]
 
 The checkpoint is loaded weights-only (FaceEnhanceNet.from_pretrained); the images come from
 get_dataloader(mode='val') -- the full images, in order, the last batch partial -- and LR is
@@ -12,7 +12,10 @@ captured inference engine and one fused metrics call per batch, with one host re
 measures.  --model esrgan evaluates the ESRGAN comparison baseline instead (a 23-block RRDBNet;
 --checkpoint is its state dict -- plain, or under 'params_ema' / 'params' -- or absent for random
 weights with a warning): the same loader, LR synthesis and fused fen_image_metrics call per batch,
-the forward run eagerly at whatever size the images have.  Prints psnr_mean / psnr_std /
+the forward run eagerly at whatever size the images have.  --model transfer evaluates a
+TransferSRModel the same way: --checkpoint is its state dict, plain or under 'model_state_dict' /
+'state_dict', with an optional 'model_config' (the Trainer's checkpoints) or 'config' dict; its
+TransferModelConfig fields are used, other keys ignored.  Prints psnr_mean / psnr_std /
 ssim_mean / ssim_std / num_images; --json OUT writes them with the per-image arrays.
 """
 import argparse
@@ -26,8 +29,8 @@ sys.path.insert(0, str(PKG))
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="PSNR / SSIM of a FaceEnhanceNet checkpoint over a validation set")
-    ap.add_argument("--model", choices=["custom", "esrgan"], default="custom",
-                    help="custom: FaceEnhanceNet (default); esrgan: the RRDBNet baseline")
+    ap.add_argument("--model", choices=["custom", "esrgan", "transfer"], default="custom",
+                    help="custom: FaceEnhanceNet (default); esrgan: the RRDBNet baseline; transfer: TransferSRModel")
     ap.add_argument("--checkpoint", default=None,
                     help="a reference-format .pth checkpoint (required for --model custom; esrgan: a RRDBNet "
                          "state dict, or none for random weights)")
@@ -42,7 +45,7 @@ def parse_args(argv=None):
     ap.add_argument("--quantize", action="store_true", help="quantise SR to 8 bits before measuring")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the results and per-image arrays here")
     args = ap.parse_args(argv)
-    if args.model == "custom" and not args.checkpoint:
+    if args.model in ("custom", "transfer") and not args.checkpoint:
         ap.error("the following arguments are required: --checkpoint")
     return args
 
@@ -54,11 +57,8 @@ def evaluate_esrgan(args, loader):
     MetricCalculator.evaluate_dataset's: PSNR over images, SSIM over per-batch means."""
     import warnings
 
-    import numpy as np
     import torch
 
-    from src.evaluation.metrics import FLAG_CLAMP, FLAG_QUANTIZE, image_metrics
-    from src.hip import lib as L
     from src.models import RRDBNet
     model = RRDBNet(precision=args.precision or "fp32")
     if args.checkpoint:
@@ -70,6 +70,36 @@ def evaluate_esrgan(args, loader):
         model.load_state_dict(state, strict=False)
     else:
         warnings.warn("--model esrgan without --checkpoint: randomly initialised weights (for testing only)")
+    return eager_metrics(model, args, loader)
+
+
+def evaluate_transfer(args, loader):
+    """A TransferSRModel checkpoint over `loader`, measured as the baseline is (eager_metrics)."""
+    from dataclasses import fields
+
+    import torch
+
+    from src.models import TransferModelConfig, TransferSRModel
+    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
+    known = {f.name for f in fields(TransferModelConfig)}
+    cfg = (ckpt.get("model_config") or ckpt.get("config")) if isinstance(ckpt, dict) else None
+    cfg = TransferModelConfig(**{k: v for k, v in cfg.items() if k in known}) if isinstance(cfg, dict) else None
+    for key in ("model_state_dict", "state_dict"):
+        if isinstance(ckpt, dict) and key in ckpt:
+            ckpt = ckpt[key]
+            break
+    model = TransferSRModel(cfg, precision=args.precision or "fp32")
+    model.load_state_dict(ckpt)
+    return eager_metrics(model, args, loader)
+
+
+def eager_metrics(model, args, loader):
+    """model's eager forward over `loader` -> the statistics of evaluate_esrgan's docstring."""
+    import numpy as np
+    import torch
+
+    from src.evaluation.metrics import FLAG_CLAMP, FLAG_QUANTIZE, image_metrics
+    from src.hip import lib as L
     model = model.to("cuda").eval()
     flags = FLAG_CLAMP | (FLAG_QUANTIZE if args.quantize else 0)
     lib = L.load()
@@ -108,12 +138,12 @@ def main(argv=None) -> int:
         raise SystemExit("evaluate.py: give --data-root DIR or --synthetic N")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate.py: the HIP path needs a ROCm GPU")
-    if args.model == "esrgan":
+    if args.model in ("esrgan", "transfer"):
         loader = get_dataloader(args.data_root, mode="val", batch_size=args.batch_size, num_workers=args.num_workers,
                                 hr_patch_size=args.hr_size, synthetic=args.synthetic, device="cpu")
-        res = evaluate_esrgan(args, loader)
+        res = evaluate_esrgan(args, loader) if args.model == "esrgan" else evaluate_transfer(args, loader)
         per = res.pop("per_image")
-        res.update(model="esrgan", checkpoint=str(args.checkpoint), precision=args.precision or "fp32",
+        res.update(model=args.model, checkpoint=str(args.checkpoint), precision=args.precision or "fp32",
                    quantize=bool(args.quantize))
         print(json.dumps(res))
         if args.json:

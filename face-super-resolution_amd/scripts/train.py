@@ -6,7 +6,8 @@ Single GPU:   python scripts/train.py --config configs/stages/stage1_psnr_config
                   scripts/train.py --config ... --perceptual-weight 0
 Every reference flag and YAML key is parsed; new flags: --precision {fp32,bf16} and
 --synthetic N (N seeded random HR images instead of a data directory; without it a missing
---data-root is an error).  loss.gan.weight > 0 builds the discriminator and GANLoss (stage 3).
+--data-root is an error).  loss.gan.weight > 0 builds the discriminator and GANLoss (stage 3).  --model transfer (or model.type:
+transfer) builds TransferSRModel from the model.transfer.* keys and trains its stage 1 (head only).
 """
 import argparse
 import os
@@ -25,7 +26,7 @@ import yaml  # noqa: E402
 
 from src.data import get_dataloader  # noqa: E402
 from src.losses import create_loss_function  # noqa: E402
-from src.models import create_face_enhance_net  # noqa: E402
+from src.models import create_face_enhance_net, create_transfer_model  # noqa: E402
 from src.models.discriminator import GANLoss, create_discriminator  # noqa: E402
 from src.training import Trainer, TrainerConfig, overfit_test  # noqa: E402
 
@@ -58,8 +59,18 @@ def resolve_precision(cli: Optional[str], tr_cfg: dict) -> str:
 
 
 def create_model(model_type: str, config: dict, precision: str):
+    if model_type == "transfer":
+        # the reference's model.transfer.* keys (scripts/train.py:69-77, configs/transfer_config.yaml).  The
+        # model starts in STAGE1_HEAD_ONLY, the stage whose backward exists on this path; the Trainer takes
+        # its get_trainable_params() groups (their learning rates are the model's, not --lr)
+        tc = config.get("model", {}).get("transfer", {})
+        return create_transfer_model(backbone_blocks=tc.get("backbone_blocks", 16),
+                                     freeze_blocks=tc.get("freeze_blocks", 16), head_blocks=tc.get("head_blocks", 4),
+                                     head_channels=tc.get("head_channels", 64),
+                                     scale_factor=tc.get("scale_factor", 4), precision=precision)
     if model_type != "custom":
-        raise ValueError(f"model type {model_type!r}: only 'custom' (FaceEnhanceNet) is built on this MI355X path")
+        raise ValueError(f"model type {model_type!r}: 'custom' (FaceEnhanceNet) and 'transfer' (TransferSRModel) "
+                         "are built on this MI355X path")
     mc = config.get("model", {}).get("custom", {})
     return create_face_enhance_net(num_channels=mc.get("num_channels", 64), num_groups=mc.get("num_groups", 3),
                                    blocks_per_group=mc.get("blocks_per_group", 4),

@@ -24,6 +24,7 @@ EPI_POOL = 32
 EPI_LAST = 64
 EPI_DOT = 128
 EPI_RELU_BWD = 4096
+EPI_NOSKIP = 8192
 
 
 class AdamwJob(Structure):

@@ -682,9 +682,11 @@ class Forward:
 
     def tail(self, feat: torch.Tensor, feat0: torch.Tensor, x_lr: torch.Tensor, training: bool,
              out: Optional[torch.Tensor] = None, hr: Optional[torch.Tensor] = None, l1_scale: float = 0.0,
-             fb: Optional[torch.Tensor] = None):
+             fb: Optional[torch.Tensor] = None, skip: bool = True):
         """conv_after_body + skip, upsampler, conv_last + bicubic skip (+ clamp / + L1 grad).
-        fb given: conv_after_body's output, already computed (the chained body launch)."""
+        fb given: conv_after_body's output, already computed (the chained body launch).
+        skip=False: conv_last without the bicubic skip and without a clamp (FEN_EPI_NOSKIP; the
+        transfer model's head, x_lr unused)."""
         s, ctx, Wt, p = self.s, self.ctx, self.Wt, self.Wt.p
         B, H, W, C = feat.shape
         fb_given = fb is not None
@@ -738,9 +740,14 @@ class Forward:
             if hr is not None:
                 dout = ctx.alloc((B, hh, ww, 16)) if self.save else ctx.scratch("dout", (B, hh, ww, 16))
                 loss_part = ctx.scratch("loss_part", (B * tiles(hh, ww), 1), torch.float32)
-            conv(ctx, h, Wt.packed("conv_last", 0), bc, hh, ww, C, s.out_ch, bias=p["conv_last.bias"],
-                 epi=L.EPI_LAST, y=out[b0:b0 + bc], lr=x_lr[b0:b0 + bc], scale=s.scale, clamp=0 if training else 1,
-                 hr=hr, dout=dout, l1_scale=l1_scale, loss_part=loss_part)
+            if skip:
+                conv(ctx, h, Wt.packed("conv_last", 0), bc, hh, ww, C, s.out_ch, bias=p["conv_last.bias"],
+                     epi=L.EPI_LAST, y=out[b0:b0 + bc], lr=x_lr[b0:b0 + bc], scale=s.scale,
+                     clamp=0 if training else 1, hr=hr, dout=dout, l1_scale=l1_scale, loss_part=loss_part)
+            else:
+                conv(ctx, h, Wt.packed("conv_last", 0), bc, hh, ww, C, s.out_ch, bias=p["conv_last.bias"],
+                     epi=L.EPI_LAST | L.EPI_NOSKIP, y=out[b0:b0 + bc], hr=hr, dout=dout, l1_scale=l1_scale,
+                     loss_part=loss_part)
         saved = dict(feat=feat, fb=fb, stages=stages, a_last=h, dout=dout, loss_part=loss_part, Ho=hh, Wo=ww)
         return out, saved
 
@@ -976,6 +983,21 @@ class Backward:
     def tail(self, sv: dict) -> torch.Tensor:
         """Backward of conv_last, the upsampler and conv_after_body; returns d(body output).
         sv['dout'] holds dL/dsr (written by the conv_last epilogue); stores d(fb) in sv['d_fb']."""
+        s, ctx, Wt = self.s, self.ctx, self.Wt
+        C = s.C
+        B = sv["dout"].shape[0]
+        d_fb = self.up(sv, flush=False)
+        H, W = sv["stages"][0]["H"], sv["stages"][0]["W"]
+        self._wg("conv_after_body", sv["feat"], d_fb, B, H, W, C, C)
+        d_body = ctx.scratch("bw_d_body", (B, H, W, C))
+        conv(ctx, d_fb, Wt.packed("conv_after_body", 2), B, H, W, C, C, y=d_body)
+        sv["d_fb"] = d_fb
+        self.cs.flush()
+        return d_body
+
+    def up(self, sv: dict, flush: bool = True) -> torch.Tensor:
+        """Backward of conv_last (with or without the bicubic skip: it has no parameters) and the
+        upsampler stages; returns d(the upsampler's input).  sv as tail()'s."""
         s, ctx, Wt, p, G = self.s, self.ctx, self.Wt, self.Wt.p, self.G
         C = s.C
         B, Ho, Wo = sv["dout"].shape[0], sv["Ho"], sv["Wo"]
@@ -1022,13 +1044,9 @@ class Backward:
             else:
                 d_fb = ctx.scratch("bw_d_fb", (B, hh, ww, C))
                 conv(ctx, du, Wt.packed(key + "conv", 2), B, hh, ww, 4 * C, C, y=d_fb)
-        H, W = stages[0]["H"], stages[0]["W"]
-        self._wg("conv_after_body", sv["feat"], d_fb, B, H, W, C, C)
-        d_body = ctx.scratch("bw_d_body", (B, H, W, C))
-        conv(ctx, d_fb, Wt.packed("conv_after_body", 2), B, H, W, C, C, y=d_body)
-        sv["d_fb"] = d_fb
-        self.cs.flush()
-        return d_body
+        if flush:
+            self.cs.flush()
+        return d_fb
 
     def head(self, x_lr: torch.Tensor, d_feat0: torch.Tensor) -> None:
         s, ctx, G = self.s, self.ctx, self.G

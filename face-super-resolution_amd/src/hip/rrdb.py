@@ -62,9 +62,10 @@ def _slopes(ctx: Ctx) -> torch.Tensor:
     return t
 
 
-def forward(ctx: Ctx, W, x: torch.Tensor, num_block: int, num_out_ch: int) -> torch.Tensor:
-    """RRDBNet.forward (reference esrgan.py:54-66): x NCHW fp32 [B,Ci,H,W] on the GPU -> NCHW fp32
-    [B,num_out_ch,4H,4W].  W: Weights over the module's state_dict keys."""
+def trunk(ctx: Ctx, W, x: torch.Tensor, num_block: int) -> torch.Tensor:
+    """feat + conv_body(body(feat)), feat = conv_first(x) (reference esrgan.py:54-57; the transfer
+    model's backbone, transfer.py:257-264): x NCHW fp32 [B,Ci,H,W] on the GPU -> NHWC [B,H,W,64] of
+    the compute dtype.  W: Weights with the keys conv_first.*, body.N.rdbM.convK.*, conv_body.*."""
     B, Ci, H, Wd = (int(v) for v in x.shape)
     bufs = [ctx.alloc((B, H, Wd, STRIDE)) for _ in range(min(4, 3 * num_block + 1))]
     feat = ctx.alloc((B, H, Wd, FEAT))
@@ -77,6 +78,14 @@ def forward(ctx: Ctx, W, x: torch.Tensor, num_block: int, num_out_ch: int) -> to
     body = ctx.alloc((B, H, Wd, FEAT))
     rrdb_conv(ctx, bufs[n % 4], STRIDE, W.packed("conv_body", 0), W.p["conv_body.bias"], body, FEAT, 0, B, H, Wd,
               FEAT, FEAT, r1=feat, r1_stride=FEAT, s1=1.0)
+    return body
+
+
+def forward(ctx: Ctx, W, x: torch.Tensor, num_block: int, num_out_ch: int) -> torch.Tensor:
+    """RRDBNet.forward (reference esrgan.py:54-66): x NCHW fp32 [B,Ci,H,W] on the GPU -> NCHW fp32
+    [B,num_out_ch,4H,4W].  W: Weights over the module's state_dict keys."""
+    B, _, H, Wd = (int(v) for v in x.shape)
+    body = trunk(ctx, W, x, num_block)
     # nearest x2 -> conv -> LeakyReLU, twice: the upsample is the gather's (h >> 1, w >> 1)
     t = body
     for s, name in ((2, "conv_up1"), (4, "conv_up2")):

@@ -158,7 +158,18 @@ class Trainer:
         self.device = torch.device("cuda", local)
         torch.cuda.set_device(self.device)
         self.model = model.to(self.device)
-        if self.world > 1:  # identical start on every rank (RCCL broadcast of the flat arena)
+        # a model that hands out its own parameter groups (TransferSRModel.get_trainable_params:
+        # the stage's learning rates, frozen parameters left out) trains on the module autograd
+        # path with a torch-format AdamW over those groups: no flat arena (it would span the
+        # frozen backbone), no fused engine
+        self._groups = self.model.get_trainable_params() if hasattr(self.model, "get_trainable_params") else None
+        if self._groups is not None:
+            if self.world > 1:
+                raise NotImplementedError("a model with parameter groups (the transfer model) trains on one GPU: the "
+                                          "bucketed gradient exchange is built over the flat arena")
+            if not self._groups:
+                raise ValueError("the model's get_trainable_params() is empty: nothing to train")
+        elif self.world > 1:  # identical start on every rank (RCCL broadcast of the flat arena)
             flatten_params(self.model, self.device)
             broadcast_arena(self.model._fen_flat, src=0)
         elif getattr(self.model, "_fen_flat", None) is None:
@@ -170,15 +181,23 @@ class Trainer:
         self.fused_ssim = getattr(loss_fn, "fused_ssim_weight", 0.0)
         if self.fused_l1 is None and isinstance(loss_fn, nn.L1Loss):
             self.fused_l1 = 1.0
-        # torch AdamW object = param_groups/lr holder for the schedulers and the checkpoint
-        # format; the update itself is the fused HIP kernel
-        self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=self.config.learning_rate,
-                                           weight_decay=self.config.weight_decay)
+        if self._groups is not None:
+            # the unfused path only; each group keeps the learning rate the model gave it
+            self.fused_l1 = self.fused_perceptual = None
+            self.fused_ssim = 0.0
+            self.optimizer = HipAdamW(self._groups, lr=self.config.learning_rate,
+                                      weight_decay=self.config.weight_decay, capturable=False)
+            self.adam_state = None
+        else:
+            # torch AdamW object = param_groups/lr holder for the schedulers and the checkpoint
+            # format; the update itself is the fused HIP kernel
+            self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=self.config.learning_rate,
+                                               weight_decay=self.config.weight_decay)
+            # the generator's one AdamW state: every engine's update program and the module-path
+            # FusedAdamW step on these buffers, so switching paths keeps moments and step count
+            self.adam_state = adamw_state(self.model._fen_flat)
+            self.adam_state[2][3] = self.lr
         self.scheduler = self._create_scheduler()
-        # the generator's one AdamW state: every engine's update program and the module-path
-        # FusedAdamW step on these buffers, so switching paths keeps moments and step count
-        self.adam_state = adamw_state(self.model._fen_flat)
-        self.adam_state[2][3] = self.lr
         self._engines: Dict[tuple, FENEngine] = {}
         self._generic_opt: Optional[FusedAdamW] = None
         self._flat_g: Optional[torch.Tensor] = None
@@ -274,6 +293,8 @@ class Trainer:
         """Any other content loss: module autograd path + RCCL grad all-reduce + fused AdamW
         (only on the accumulation step, `update`; the loss is divided by accumulation_steps as
         trainer.py:477 does)."""
+        if self._groups is not None:
+            return self._grouped_step(hr, update)
         self._dp_exchanges()
         lr = bicubic_down4(hr)
         sr = self.model(lr)
@@ -285,6 +306,21 @@ class Trainer:
         (loss / (self.world * self._accum())).backward()
         if update:
             self._apply_generic_update()
+        return loss.detach()
+
+    def _grouped_step(self, hr: torch.Tensor, update: bool = True) -> torch.Tensor:
+        """The same iteration for a model with parameter groups: module autograd, then
+        clip_grad_norm_ over the trainable parameters and the grouped AdamW step (HipAdamW:
+        fen_adamw_multi per group).  Frozen parameters get no gradient and are in no group."""
+        sr = self.model(bicubic_down4(hr))
+        loss = self._content(sr, hr)
+        self.optimizer.zero_grad(set_to_none=True)
+        (loss / self._accum()).backward()
+        if update:
+            if self.config.gradient_clip and self.config.gradient_clip > 0:
+                torch.nn.utils.clip_grad_norm_([p for g in self.optimizer.param_groups for p in g["params"]],
+                                               self.config.gradient_clip)
+            self.optimizer.step()
         return loss.detach()
 
     def _content(self, sr: torch.Tensor, hr: torch.Tensor) -> torch.Tensor:
@@ -551,6 +587,8 @@ class Trainer:
 
     def _optimizer_state(self) -> Dict:
         """The generator's AdamW state in torch.optim.AdamW's format (empty before a step)."""
+        if self._groups is not None:
+            return self.optimizer.state_dict()
         view = self._adam_view()
         return view.state_dict() if view.steps > 0 else self.optimizer.state_dict()
 
@@ -569,6 +607,10 @@ class Trainer:
             "training_history": self.training_history,
             "config": dict(self.config.__dict__),
         }
+        import dataclasses
+        mc = getattr(self.model, "config", None)
+        if self._groups is not None and dataclasses.is_dataclass(mc):
+            ckpt["model_config"] = dataclasses.asdict(mc)      # what evaluate.py --model transfer rebuilds from
         if self.use_gan:
             ckpt["discriminator_state_dict"] = {k: v.detach().cpu() for k, v in self.discriminator.state_dict().items()}
             ckpt["optimizer_d_state_dict"] = self.optimizer_d.state_dict()
@@ -587,7 +629,8 @@ class Trainer:
         osd = ckpt.get("optimizer_state_dict")
         if osd:
             self.optimizer.load_state_dict(osd)
-            self._adam_view().load_state_dict(osd)   # the one state both step paths use
+            if self._groups is None:
+                self._adam_view().load_state_dict(osd)   # the one state both step paths use
         if self.scheduler and ckpt.get("scheduler_state_dict"):
             self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])
         self.current_epoch = ckpt["epoch"] + 1

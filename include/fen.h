@@ -43,9 +43,16 @@ enum {
     FEN_EPI_POOL = 32,      /* part[b][tile][co] = sum over the tile's pixels of the stored v   */
     FEN_EPI_LAST = 64,      /* conv_last: + bicubic skip, eval clamp, NCHW fp32 out, L1 grad    */
     FEN_EPI_DOT = 128,      /* part[b][tile][co] = sum over the tile of (stored v) * pre_in      */
-    FEN_EPI_RELU_BWD = 4096 /* y = pre_in>0 ? v : 0 (ReLU backward through the ReLU output pre_in;
+    FEN_EPI_RELU_BWD = 4096,/* y = pre_in>0 ? v : 0 (ReLU backward through the ReLU output pre_in;
                                no partial sums: the frozen VGG19 extractor's data gradients,
                                perceptual.py:60-64).  Not with PRELU_BWD / DOT / LAST / SHUFFLE.  */
+    FEN_EPI_NOSKIP = 8192   /* with FEN_EPI_LAST only: conv_last without the bicubic skip and without
+                               a clamp (the transfer model's, transfer.py:77,89): NCHW fp32 out and
+                               the optional L1 epilogue as FEN_EPI_LAST; lr must be NULL, scale and
+                               clamp 0 (FEN_EINVAL otherwise).  16-bit, Cin 64, whole 16x16 tiles run
+                               the streaming conv_last kernel; any other shape runs as
+                               fen_rrdb_conv(nchw_out = 1), which needs FEN_EPI_BIAS and has no L1
+                               epilogue: with hr given such a shape is FEN_EUNSUPPORTED.          */
 };
 
 /* 3x3, stride 1, pad 1 convolution as an implicit GEMM on MFMA.
