@@ -1,6 +1,7 @@
 // ESRGAN baseline (RRDBNet, reference src/models/esrgan.py:17-103): 3x3 / stride 1 / pad 1
 // convolutions over a GROWING CHANNEL CONCATENATION, as implicit GEMMs on MFMA (gfx950).
-// Inference only.
+// The forward first; the dense blocks' backward (k_rrdb_dgrad, fen_rrdb_dgrad, fen_rrdb_block_bwd:
+// the transfer model's stages 2 and 3) follows it, and its weight gradients are in wgrad.hip.
 //
 // A ResidualDenseBlock (esrgan.py:85-103) lives in ONE NHWC buffer of 192 channels per pixel,
 //     x (0..63) | x1 (64..95) | x2 (96..127) | x3 (128..159) | x4 (160..191),
@@ -256,6 +257,171 @@ int dispatch_rrdb(const fen_rrdb_conv_desc* d, hipStream_t s) {
     return launch_rrdb<T, 16>(d, s);
 }
 
+// ---- backward: the data gradient of a dense block's conv (fen_rrdb_dgrad) ----
+// dx[.., 0:Cout) (+)= s * conv(dy[.., dy_off : dy_off + Cin); wt), wt = fen_pack_conv_w mode 2
+// ([9][Cout][Cin], taps flipped): the forward's implicit GEMM with a NARROW K (Cin = 32 or 64:
+// one 128-B panel in 16 bits, one or two in fp32) and a WIDE N (Cout = 64..192).  The dy halo --
+// every panel of it -- is therefore staged in LDS ONCE per 16 x 16 tile and the 64-row output-
+// channel tiles loop over it; only the weights stream, per (channel tile, panel, tap), through
+// the forward's double-buffered LDS tile with one barrier per step.  Rows >= Cout of the last
+// channel tile (Cout = 96, 160) are zero weights, never stored.  Epilogue per 4 channels: v =
+// s acc (+ what dx holds) (+ s1 r1 + s2 r2 on channels 0..63), times LeakyReLU'(act) -- act > 0 ?
+// 1 : 0.2 on the stored forward output -- on the top 32 channels written; one store in dtype.
+// A tile reads dy's channel range of its halo and rewrites only its own pixels of dx's [0, Cout):
+// the ranges are disjoint (refused otherwise), so tiles are independent; no atomics, fixed order.
+// LDS: NPAN x 41.5 KB halo + 16 KB weights (bf16 56.5 KB, two blocks per CU; fp32 97 KB, one).
+template <typename T, int NPAN>
+__global__ __launch_bounds__(256) void k_rrdb_dgrad(const fen_rrdb_dgrad_desc d) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* halo = smem;                          // [NPAN][HALO_BYTES]
+    char* wbuf = smem + NPAN * HALO_BYTES;      // [2][64 rows][128 B]
+    constexpr int COT = 64, MT = 4;
+    constexpr int WPT = COT * 8 / 256;          // 2 weight chunks per thread and step
+    constexpr int HPT = (HP * 8 + 255) / 256;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = lane >> 4, c16 = lane & 15;
+    const int H = d.H, W = d.W, Cout = d.Cout;
+    const int twn = (W + 15) >> 4, tpi = twn * ((H + 15) >> 4);
+    const int tb = xcd_block();
+    const int b = tb / tpi, tile = tb - b * tpi;
+    const int h0 = (tile / twn) << 4, w0 = (tile % twn) << 4;
+    const char* yb = (const char*)d.dy + (size_t)d.dy_off * sizeof(T);
+    const char* wb = (const char*)d.w;
+    const size_t ypix = (size_t)d.dy_stride * sizeof(T);
+    const int cinb = d.Cin * (int)sizeof(T);    // bytes of a pixel's dy slice: 64, 128 or 256
+    const int npan = (cinb + 127) >> 7;         // <= NPAN (dispatch)
+    const int nct = (Cout + COT - 1) / COT;
+
+    uint4 wr[WPT];
+    auto load_w = [&](int ct, int pn, int tap) {
+#pragma unroll
+        for (int j = 0; j < WPT; ++j) {
+            const int i = tid + j * 256;
+            const int r = i >> 3, ch = i & 7;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (ct * COT + r < Cout && pn * 128 + ch * 16 < cinb)
+                v = *(const uint4*)(wb + (size_t)(tap * Cout + ct * COT + r) * cinb + pn * 128 + ch * 16);
+            wr[j] = v;
+        }
+    };
+    auto store_w = [&](char* dst) {
+#pragma unroll
+        for (int j = 0; j < WPT; ++j) {
+            const int i = tid + j * 256;
+            *(uint4*)(dst + swz(i >> 3, i & 7)) = wr[j];
+        }
+    };
+
+    // the whole dy halo, once: zero padding, ragged tiles and chunks past Cin are zeros
+    load_w(0, 0, 0);
+    for (int pn = 0; pn < npan; ++pn) {
+        uint4 hv[HPT];
+#pragma unroll
+        for (int j = 0; j < HPT; ++j) {
+            const int i = tid + j * 256;
+            const int p = i >> 3, ch = i & 7;
+            const int hr = p / HALO, hc = p - hr * HALO;
+            const int gh = h0 + hr - 1, gw = w0 + hc - 1;
+            const bool ok = i < HP * 8 && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W &&
+                            pn * 128 + ch * 16 < cinb;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (ok) v = *(const uint4*)(yb + ((size_t)(b * H + gh) * W + gw) * ypix + pn * 128 + ch * 16);
+            hv[j] = v;
+        }
+#pragma unroll
+        for (int j = 0; j < HPT; ++j) {
+            const int i = tid + j * 256;
+            if (i < HP * 8) *(uint4*)(halo + pn * HALO_BYTES + hswz(i >> 3, i & 7)) = hv[j];
+        }
+    }
+    store_w(wbuf);
+    __syncthreads();
+
+    const int w_ = w0 + c16;
+    const int act0 = Cout - RRDB_GROW;          // first channel the activation derivative scales
+    int par = 0;
+    for (int ct = 0; ct < nct; ++ct) {
+        f32x4 acc[MT][4];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int pn = 0; pn < npan; ++pn) {
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap) {
+                // the step after this one: next tap, next panel, or the next channel tile's first
+                const bool more = tap < 8 || pn + 1 < npan || ct + 1 < nct;
+                if (more) {
+                    if (tap < 8) load_w(ct, pn, tap + 1);
+                    else if (pn + 1 < npan) load_w(ct, pn + 1, 0);
+                    else load_w(ct + 1, 0, 0);
+                }
+                rrdb_tap<T, MT>(acc, wbuf + par * (COT * 128), halo + pn * HALO_BYTES, tap, wave, q, c16);
+                if (more) store_w(wbuf + (par ^ 1) * (COT * 128));
+                __syncthreads();
+                par ^= 1;
+            }
+        }
+        // ---- epilogue: acc[m][n][r] = D[ct*64 + m*16 + 4q + r][pixel (h0 + 4 wave + n, w0 + c16)] ----
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int cob = ct * COT + m * 16 + q * 4;
+            if (cob >= Cout) continue;
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                // one pixel's loads at a time: hoisted together, the 16 x 4 operand loads of the
+                // tile's epilogue spill
+                __builtin_amdgcn_sched_barrier(0);
+                const int h = h0 + wave * 4 + n;
+                if (h >= H || w_ >= W) continue;
+                const size_t pix = (size_t)(b * H + h) * W + w_;
+                char* dxp = (char*)d.dx + (pix * d.dx_stride + cob) * sizeof(T);
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = acc[m][n][r] * d.s;
+                if (d.accumulate) {
+                    float o[4];
+                    ld4<T>(dxp, o);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] += o[r];
+                }
+                if (cob < RRDB_FEAT) {
+                    if (d.r1) {
+                        float rv[4];
+                        ld4<T>((const char*)d.r1 + (pix * d.r1_stride + cob) * sizeof(T), rv);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] += d.s1 * rv[r];
+                    }
+                    if (d.r2) {
+                        float rv[4];
+                        ld4<T>((const char*)d.r2 + (pix * d.r2_stride + cob) * sizeof(T), rv);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] += d.s2 * rv[r];
+                    }
+                }
+                if (d.act && cob >= act0) {
+                    float a[4];
+                    ld4<T>((const char*)d.act + (pix * d.act_stride + cob) * sizeof(T), a);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = prelu_bwd_f(v[r], a[r], RRDB_SLOPE);
+                }
+                st4<T>(dxp, v);
+            }
+        }
+    }
+}
+
+template <typename T, int NPAN>
+int launch_rrdb_dgrad(const fen_rrdb_dgrad_desc* d, hipStream_t s) {
+    constexpr int LDS = NPAN * HALO_BYTES + 2 * 64 * 128;
+    const int tpi = ((d->W + 15) >> 4) * ((d->H + 15) >> 4);
+    fen_detail::opt_in_lds<k_rrdb_dgrad<T, NPAN>>(LDS);
+    hipLaunchKernelGGL((k_rrdb_dgrad<T, NPAN>), dim3((unsigned)(d->B * tpi)), dim3(256), LDS, s, *d);
+    FEN_CHECK_LAUNCH();
+    return FEN_OK;
+}
+
 // pixel indices and the grid's x dimension are ints in the kernels
 bool pixels_ok(int B, int H, int W) { return (size_t)B * (size_t)H * (size_t)W < ((size_t)1 << 31); }
 
@@ -329,4 +495,110 @@ extern "C" int fen_rrdb_first(int dtype, int B, int Ci, int H, int W, const floa
         FEN_CHECK_LAUNCH();
         return FEN_OK;
     });
+}
+
+extern "C" int fen_rrdb_dgrad(const fen_rrdb_dgrad_desc* d, void* stream) {
+    if (!d || !d->dy || !d->w || !d->dx) return FEN_EINVAL;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return FEN_EINVAL;
+    if (fen_detail::check_dtype(d->dtype) != FEN_OK) return FEN_EINVAL;
+    if (d->dtype == FEN_F16) return FEN_EUNSUPPORTED;   // fp16 is inference-only
+    if (((uintptr_t)d->dy | (uintptr_t)d->w | (uintptr_t)d->dx | (uintptr_t)d->r1 | (uintptr_t)d->r2 |
+         (uintptr_t)d->act) & 15)
+        return FEN_EINVAL;
+    const int esz = d->dtype == FEN_F32 ? 4 : 2;
+    if ((d->Cin != RRDB_GROW && d->Cin != RRDB_FEAT) || d->Cout < RRDB_FEAT || d->Cout > RRDB_STRIDE ||
+        (d->Cout - RRDB_FEAT) % RRDB_GROW)
+        return FEN_EUNSUPPORTED;
+    if (d->dy_off < 0 || d->dy_stride < d->dy_off + d->Cin || (d->dy_stride * esz) % 16 || (d->dy_off * esz) % 16)
+        return FEN_EINVAL;
+    if (d->dx_stride < d->Cout || (d->dx_stride * esz) % 16) return FEN_EINVAL;
+    if ((d->r1 && (d->r1_stride < RRDB_FEAT || (d->r1_stride * esz) % 16)) ||
+        (d->r2 && (d->r2_stride < RRDB_FEAT || (d->r2_stride * esz) % 16)) ||
+        (d->act && (d->act_stride < d->Cout || (d->act_stride * esz) % 16)))
+        return FEN_EINVAL;
+    // in place (a block's gradient buffer): the slice read lies past every channel written
+    if (d->dy == d->dx && d->dy_off < d->Cout) return FEN_EINVAL;
+    if (!pixels_ok(d->B, d->H, d->W)) return FEN_EUNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (d->dtype == FEN_BF16) return launch_rrdb_dgrad<bf16, 1>(d, s);
+    return d->Cin * 4 <= 128 ? launch_rrdb_dgrad<float, 1>(d, s) : launch_rrdb_dgrad<float, 2>(d, s);
+}
+
+extern "C" size_t fen_rrdb_block_bwd_work_floats(int dtype, int B, int H, int W) {
+    size_t need = 0;
+    for (int k = 0; k < 5; ++k) {
+        fen_rrdb_wgrad_desc g = {};
+        g.dtype = dtype; g.B = B; g.H = H; g.W = W;
+        g.Cin = RRDB_FEAT + RRDB_GROW * k;
+        g.Cout = k < 4 ? RRDB_GROW : RRDB_FEAT;
+        const size_t n = fen_rrdb_wgrad_work_floats(&g);
+        if (n > need) need = n;
+    }
+    return need;
+}
+
+extern "C" int fen_rrdb_block_bwd(const fen_rrdb_block_bwd_desc* d, void* stream) {
+    if (!d || !d->buf || !d->D || !d->g) return FEN_EINVAL;
+    bool any_w = false;
+    for (int k = 0; k < 5; ++k) {
+        if (!d->wt[k]) return FEN_EINVAL;
+        if (d->db[k] && !d->dw[k]) return FEN_EINVAL;
+        any_w = any_w || d->dw[k];
+    }
+    if (any_w && !d->work) return FEN_EINVAL;
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->num_feat <= 0 || d->num_grow_ch <= 0) return FEN_EINVAL;
+    if (fen_detail::check_dtype(d->dtype) != FEN_OK) return FEN_EINVAL;
+    if (d->dtype == FEN_F16) return FEN_EUNSUPPORTED;
+    if (d->D == d->buf || d->g == d->D || d->g_rrdb == d->D) return FEN_EINVAL;
+    if (d->num_feat != RRDB_FEAT || d->num_grow_ch != RRDB_GROW) return FEN_EUNSUPPORTED;
+    if (!pixels_ok(d->B, d->H, d->W)) return FEN_EUNSUPPORTED;
+    // the third block of an RRDB sits behind `out * 0.2 + x_rrdb`: its incoming gradient is 0.2 g
+    const float gs = d->third ? RRDB_SLOPE : 1.f;
+    for (int k = 4; k >= 0; --k) {
+        fen_rrdb_dgrad_desc c = {};
+        c.dtype = d->dtype;
+        c.B = d->B; c.H = d->H; c.W = d->W;
+        c.Cout = RRDB_FEAT + RRDB_GROW * k;
+        c.w = d->wt[k];
+        c.dx = d->D; c.dx_stride = RRDB_STRIDE;
+        if (k == 4) {      // conv5: D = 0.2 dgrad(g) on all 192 channels, + g on the first 64
+            c.Cin = RRDB_FEAT;
+            c.dy = d->g; c.dy_stride = d->g_stride; c.dy_off = 0;
+            c.s = RRDB_SLOPE * gs;
+            c.r1 = d->g; c.r1_stride = d->g_stride; c.s1 = gs;
+        } else {           // conv k + 1: D[0 : Cout) += dgrad(dpre), dpre = D's slice at Cout
+            c.Cin = RRDB_GROW;
+            c.dy = d->D; c.dy_stride = RRDB_STRIDE; c.dy_off = c.Cout;
+            c.s = 1.f;
+            c.accumulate = 1;
+            if (k == 0 && d->g_rrdb) { c.r2 = d->g_rrdb; c.r2_stride = d->g_rrdb_stride; c.s2 = 1.f; }
+        }
+        if (k > 0) { c.act = d->buf; c.act_stride = RRDB_STRIDE; }   // completes x_k's slice
+        const int rc = fen_rrdb_dgrad(&c, stream);
+        if (rc != FEN_OK) return rc;
+    }
+    // the weight gradients: x = the forward buffer, dy = D's slices (dpre_1..4) and 0.2 gs g (dpre_5)
+    for (int k = 0; k < 5; ++k) {
+        if (!d->dw[k]) continue;
+        fen_rrdb_wgrad_desc g = {};
+        g.dtype = d->dtype;
+        g.B = d->B; g.H = d->H; g.W = d->W;
+        g.Cin = RRDB_FEAT + RRDB_GROW * k;
+        g.x = d->buf; g.x_stride = RRDB_STRIDE;
+        if (k < 4) {
+            g.Cout = RRDB_GROW;
+            g.dy = d->D; g.dy_stride = RRDB_STRIDE; g.dy_off = g.Cin;
+            g.scale = 1.f;
+        } else {
+            g.Cout = RRDB_FEAT;
+            g.dy = d->g; g.dy_stride = d->g_stride; g.dy_off = 0;
+            g.scale = RRDB_SLOPE * gs;
+        }
+        g.dw = d->dw[k]; g.db = d->db[k];
+        g.accumulate = d->accumulate;
+        g.work = d->work;
+        const int rc = fen_rrdb_wgrad(&g, stream);
+        if (rc != FEN_OK) return rc;
+    }
+    return FEN_OK;
 }

@@ -35,7 +35,9 @@ __device__ __forceinline__ int pan_off(int p, int c, int pbytes) {
 }
 
 template <typename T, int COT>
-__global__ __launch_bounds__(576, 1) void k_wgrad(const fen_wgrad_desc d, int tpc, float* part, float* dbpart) {
+__global__ __launch_bounds__(576, 1) void k_wgrad(const fen_wgrad_desc d, int tpc, float* part, float* dbpart, int xs,
+                                                int ys, int yoff) {
+    // xs, ys: elements between pixels of x / dy (dense: Cin / Cout); yoff: dy's first channel
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int CK = Tr<T>::CK;
     constexpr int NPX = 64 / CK;                                  // panels of the 64-ci halo
@@ -78,7 +80,7 @@ __global__ __launch_bounds__(576, 1) void k_wgrad(const fen_wgrad_desc d, int tp
             if ((unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W &&
                 (ci0 + pn * CK) * (int)sizeof(T) + ch * 16 < Cin * (int)sizeof(T))
                 v = *(const uint4*)((const char*)d.x +
-                                    (((size_t)(b * H + gh) * W + gw) * Cin + ci0 + pn * CK) * sizeof(T) + ch * 16);
+                                    (((size_t)(b * H + gh) * W + gw) * xs + ci0 + pn * CK) * sizeof(T) + ch * 16);
             *(uint4*)(hx + pn * PANEL_HALO + swz(p, ch)) = v;
         }
         for (int i = tid; i < 256 * YCH; i += 576) {
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(576, 1) void k_wgrad(const fen_wgrad_desc d, int tp
             uint4 v = make_uint4(0, 0, 0, 0);
             if (gh < H && gw < W)
                 v = *(const uint4*)((const char*)d.dy +
-                                    (((size_t)(b * H + gh) * W + gw) * Cout + co0) * sizeof(T) + j * 16);
+                                    (((size_t)(b * H + gh) * W + gw) * ys + yoff + co0) * sizeof(T) + j * 16);
             *(uint4*)(ty + pn * PANEL_TILE + swz(p, ch)) = v;
         }
         __syncthreads();
@@ -172,13 +174,13 @@ __global__ __launch_bounds__(576, 1) void k_wgrad(const fen_wgrad_desc d, int tp
     }
 }
 
-// dw[co][ci][kh][kw] (+)= sum_chunk slab[chunk][tap][co][ci];  db[co] (+)= sum_chunk dbpart
+// dw[co][ci][kh][kw] (+)= scale * sum_chunk slab[chunk][tap][co][ci];  db[co] (+)= scale * sum_chunk dbpart
 // block = 64 consecutive slab elements x 4 waves, each wave sums a quarter of the chunks
 // (independent loads in flight), fixed-order combine in LDS -> bitwise reproducible.
 __global__ __launch_bounds__(256) void k_wgrad_finalize(int nchunk, int Cout, int Cin, int cout_valid,
                                                         const float* __restrict__ part,
                                                         const float* __restrict__ dbpart, float* dw, float* db,
-                                                        int accumulate) {
+                                                        int accumulate, float scale) {
     __shared__ float red[4][64];
     const size_t per = (size_t)9 * Cout * Cin;
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(256) void k_wgrad_finalize(int nchunk, int Cout, in
     red[g][lane] = s;
     __syncthreads();
     if (g == 0 && i < per) {
-        const float t = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+        const float t = ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) * scale;
         const int ci = (int)(i % Cin);
         const int co = (int)((i / Cin) % Cout);
         const int tap = (int)(i / ((size_t)Cin * Cout));
@@ -213,6 +215,7 @@ __global__ __launch_bounds__(256) void k_wgrad_finalize(int nchunk, int Cout, in
         for (int co = lane; co < cout_valid; co += 64) {
             float t = 0.f;
             for (int c = 0; c < nchunk; ++c) t += dbpart[(size_t)c * Cout + co];
+            t *= scale;
             db[co] = accumulate ? db[co] + t : t;
         }
     }
@@ -645,6 +648,36 @@ int launch_p(int n, const fen_wgrad_desc* ds, float* work, hipStream_t s) {
     return FEN_OK;
 }
 
+// the generic kernel pair (any dtype / shape check_desc admits): x and dy at pixel strides xs / ys
+// (elements), dy's channels from yoff; the finalize multiplies by scale (1 is exact)
+int launch_generic(const fen_wgrad_desc* d, int xs, int ys, int yoff, float scale, hipStream_t s) {
+    int nchunk, tpc, cot;
+    wgrad_geom(d, 1, &nchunk, &tpc, &cot);
+    float* part = d->work;
+    float* dbpart = d->work + (size_t)nchunk * 9 * d->Cout * d->Cin;
+    dim3 grid(nchunk, d->Cout / cot, (d->Cin + 63) / 64);
+    const int rc = fen_detail::with_dtype(d->dtype, [&](auto tag) -> int {
+        using T = decltype(tag);
+        if constexpr (!std::is_same<T, f16>::value) {   // (check_desc: bf16 or f32)
+            const int npx = sizeof(T) == 2 ? 1 : 2;
+            const int npy = sizeof(T) == 2 ? 1 : (cot * 4 > 128 ? 2 : 1);
+            const size_t lds = (size_t)npx * PANEL_HALO + (size_t)npy * PANEL_TILE;
+            if (cot == 64) hipLaunchKernelGGL((k_wgrad<T, 64>), grid, dim3(576), lds, s, *d, tpc, part, dbpart, xs, ys, yoff);
+            else hipLaunchKernelGGL((k_wgrad<T, 16>), grid, dim3(576), lds, s, *d, tpc, part, dbpart, xs, ys, yoff);
+            FEN_CHECK_LAUNCH();
+            return FEN_OK;
+        }
+        return FEN_EINVAL;
+    });
+    if (rc != FEN_OK) return rc;
+    const size_t per = (size_t)9 * d->Cout * d->Cin;
+    const int nb = (int)((per + 63) / 64);
+    hipLaunchKernelGGL(k_wgrad_finalize, dim3(nb), dim3(256), 0, s, nchunk, d->Cout, d->Cin, d->cout_valid,
+                       part, dbpart, d->dw, d->db, d->accumulate, scale);
+    FEN_CHECK_LAUNCH();
+    return FEN_OK;
+}
+
 }  // namespace
 
 extern "C" size_t fen_wgrad_work_floats(const fen_wgrad_desc* d) {
@@ -671,31 +704,7 @@ extern "C" int fen_wgrad3x3(const fen_wgrad_desc* d, void* stream) {
     if (!d->work) return FEN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (wgrad_use_p(d)) return launch_p(1, d, d->work, s);
-    int nchunk, tpc, cot;
-    wgrad_geom(d, 1, &nchunk, &tpc, &cot);
-    float* part = d->work;
-    float* dbpart = d->work + (size_t)nchunk * 9 * d->Cout * d->Cin;
-    dim3 grid(nchunk, d->Cout / cot, (d->Cin + 63) / 64);
-    const int rc = fen_detail::with_dtype(d->dtype, [&](auto tag) -> int {
-        using T = decltype(tag);
-        if constexpr (!std::is_same<T, f16>::value) {   // (check_desc: bf16 or f32)
-            const int npx = sizeof(T) == 2 ? 1 : 2;
-            const int npy = sizeof(T) == 2 ? 1 : (cot * 4 > 128 ? 2 : 1);
-            const size_t lds = (size_t)npx * PANEL_HALO + (size_t)npy * PANEL_TILE;
-            if (cot == 64) hipLaunchKernelGGL((k_wgrad<T, 64>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
-            else hipLaunchKernelGGL((k_wgrad<T, 16>), grid, dim3(576), lds, s, *d, tpc, part, dbpart);
-            FEN_CHECK_LAUNCH();
-            return FEN_OK;
-        }
-        return FEN_EINVAL;
-    });
-    if (rc != FEN_OK) return rc;
-    const size_t per = (size_t)9 * d->Cout * d->Cin;
-    const int nb = (int)((per + 63) / 64);
-    hipLaunchKernelGGL(k_wgrad_finalize, dim3(nb), dim3(256), 0, s, nchunk, d->Cout, d->Cin, d->cout_valid,
-                       part, dbpart, d->dw, d->db, d->accumulate);
-    FEN_CHECK_LAUNCH();
-    return FEN_OK;
+    return launch_generic(d, d->Cin, d->Cout, 0, 1.f, s);
 }
 
 extern "C" int fen_wgrad3x3_multi(int n, const fen_wgrad_desc* ds, void* stream) {
@@ -714,4 +723,47 @@ extern "C" int fen_wgrad3x3_multi(int n, const fen_wgrad_desc* ds, void* stream)
         if (st != FEN_OK) return st;
     }
     return FEN_OK;
+}
+
+// ---- the strided weight gradient of the dense blocks (fen_rrdb_wgrad) ----
+namespace {
+int rrdb_wgrad_check(const fen_rrdb_wgrad_desc* d) {
+    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return FEN_EINVAL;
+    if (fen_detail::check_dtype(d->dtype) != FEN_OK) return FEN_EINVAL;
+    if (d->dtype == FEN_F16) return FEN_EUNSUPPORTED;   // fp16 is inference-only
+    if (d->Cin < 64 || d->Cin > 192 || (d->Cin - 64) % 32 || (d->Cout != 32 && d->Cout != 64)) return FEN_EUNSUPPORTED;
+    if ((size_t)d->B * (size_t)d->H * (size_t)d->W >= ((size_t)1 << 31)) return FEN_EUNSUPPORTED;
+    return FEN_OK;
+}
+fen_wgrad_desc rrdb_wgrad_dense(const fen_rrdb_wgrad_desc* d) {
+    fen_wgrad_desc g = {};
+    g.dtype = d->dtype;
+    g.B = d->B; g.H = d->H; g.W = d->W; g.Cin = d->Cin; g.Cout = d->Cout;
+    g.cout_valid = d->Cout;
+    g.x = d->x; g.dy = d->dy; g.dw = d->dw; g.db = d->db;
+    g.accumulate = d->accumulate;
+    g.work = d->work;
+    return g;
+}
+}  // namespace
+
+extern "C" size_t fen_rrdb_wgrad_work_floats(const fen_rrdb_wgrad_desc* d) {
+    if (!d || rrdb_wgrad_check(d) != FEN_OK) return 0;
+    const fen_wgrad_desc g = rrdb_wgrad_dense(d);
+    int nchunk, tpc, cot;
+    wgrad_geom(&g, 1, &nchunk, &tpc, &cot);
+    return (size_t)nchunk * 9 * g.Cout * g.Cin + (size_t)nchunk * g.Cout;
+}
+
+extern "C" int fen_rrdb_wgrad(const fen_rrdb_wgrad_desc* d, void* stream) {
+    if (!d || !d->x || !d->dy || !d->dw || !d->work) return FEN_EINVAL;
+    const int st = rrdb_wgrad_check(d);
+    if (st != FEN_OK) return st;
+    if (((uintptr_t)d->x | (uintptr_t)d->dy) & 15) return FEN_EINVAL;
+    const int esz = d->dtype == FEN_F32 ? 4 : 2;
+    if (d->x_stride < d->Cin || (d->x_stride * esz) % 16) return FEN_EINVAL;
+    if (d->dy_off < 0 || d->dy_stride < d->dy_off + d->Cout || (d->dy_stride * esz) % 16 || (d->dy_off * esz) % 16)
+        return FEN_EINVAL;
+    const fen_wgrad_desc g = rrdb_wgrad_dense(d);
+    return launch_generic(&g, d->x_stride, d->dy_stride, d->dy_off, d->scale, (hipStream_t)stream);
 }

@@ -26,7 +26,7 @@ import yaml  # noqa: E402
 
 from src.data import get_dataloader  # noqa: E402
 from src.losses import create_loss_function  # noqa: E402
-from src.models import create_face_enhance_net, create_transfer_model  # noqa: E402
+from src.models import TrainingStage, create_face_enhance_net, create_transfer_model  # noqa: E402
 from src.models.discriminator import GANLoss, create_discriminator  # noqa: E402
 from src.training import Trainer, TrainerConfig, overfit_test  # noqa: E402
 
@@ -58,16 +58,24 @@ def resolve_precision(cli: Optional[str], tr_cfg: dict) -> str:
     return "fp32"
 
 
-def create_model(model_type: str, config: dict, precision: str):
+def create_model(model_type: str, config: dict, precision: str, transfer_stage: Optional[int] = None):
     if model_type == "transfer":
         # the reference's model.transfer.* keys (scripts/train.py:69-77, configs/transfer_config.yaml).  The
-        # model starts in STAGE1_HEAD_ONLY, the stage whose backward exists on this path; the Trainer takes
-        # its get_trainable_params() groups (their learning rates are the model's, not --lr)
+        # model starts in STAGE1_HEAD_ONLY; --transfer-stage / model.transfer.stage 2 or 3 builds it with the
+        # RRDB backward on (train_backbone=True) and sets the stage here, before the Trainer takes its
+        # get_trainable_params() groups (their learning rates are the model's, not --lr)
         tc = config.get("model", {}).get("transfer", {})
-        return create_transfer_model(backbone_blocks=tc.get("backbone_blocks", 16),
-                                     freeze_blocks=tc.get("freeze_blocks", 16), head_blocks=tc.get("head_blocks", 4),
-                                     head_channels=tc.get("head_channels", 64),
-                                     scale_factor=tc.get("scale_factor", 4), precision=precision)
+        stage = int(transfer_stage if transfer_stage is not None else tc.get("stage", 1))
+        if stage not in (1, 2, 3):
+            raise ValueError(f"model.transfer.stage must be 1, 2 or 3 (got {stage})")
+        model = create_transfer_model(backbone_blocks=tc.get("backbone_blocks", 16),
+                                      freeze_blocks=tc.get("freeze_blocks", 16), head_blocks=tc.get("head_blocks", 4),
+                                      head_channels=tc.get("head_channels", 64),
+                                      scale_factor=tc.get("scale_factor", 4), precision=precision,
+                                      train_backbone=stage > 1)
+        if stage > 1:
+            model.set_training_stage(TrainingStage(stage))
+        return model
     if model_type != "custom":
         raise ValueError(f"model type {model_type!r}: 'custom' (FaceEnhanceNet) and 'transfer' (TransferSRModel) "
                          "are built on this MI355X path")
@@ -143,6 +151,8 @@ def main(argv=None):
     ap.add_argument("--no-wandb", action="store_true")
     ap.add_argument("--precision", type=str, default=None, choices=["fp32", "bf16"])
     ap.add_argument("--synthetic", type=int, default=0)
+    ap.add_argument("--transfer-stage", type=int, default=None, choices=[1, 2, 3],
+                    help="TransferSRModel training stage (default: model.transfer.stage, else 1)")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -167,7 +177,7 @@ def main(argv=None):
     train_loader, val_loader = build_loaders(config, data_root, batch_size, args.synthetic)
 
     precision = resolve_precision(args.precision, tr_cfg)
-    model = create_model(model_type, config, precision)
+    model = create_model(model_type, config, precision, args.transfer_stage)
     discriminator, gan_loss = create_gan(config, precision)
     gan = loss_cfg.get("gan", {})
     pw = args.perceptual_weight if args.perceptual_weight is not None else loss_cfg.get("perceptual_weight", 0.01)

@@ -138,6 +138,34 @@ class RrdbBlockDesc(Structure):     # fen_rrdb_block_desc
     ]
 
 
+class RrdbDgradDesc(Structure):    # fen_rrdb_dgrad_desc
+    _fields_ = [
+        ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
+        ("dy", c_void_p), ("dy_stride", c_int), ("dy_off", c_int), ("w", c_void_p),
+        ("dx", c_void_p), ("dx_stride", c_int), ("accumulate", c_int), ("s", c_float),
+        ("r1", c_void_p), ("r1_stride", c_int), ("s1", c_float),
+        ("r2", c_void_p), ("r2_stride", c_int), ("s2", c_float),
+        ("act", c_void_p), ("act_stride", c_int),
+    ]
+
+
+class RrdbWgradDesc(Structure):    # fen_rrdb_wgrad_desc
+    _fields_ = [
+        ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
+        ("x", c_void_p), ("x_stride", c_int), ("dy", c_void_p), ("dy_stride", c_int), ("dy_off", c_int),
+        ("scale", c_float), ("dw", c_void_p), ("db", c_void_p), ("accumulate", c_int), ("work", c_void_p),
+    ]
+
+
+class RrdbBlockBwdDesc(Structure):  # fen_rrdb_block_bwd_desc
+    _fields_ = [
+        ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("num_feat", c_int), ("num_grow_ch", c_int),
+        ("buf", c_void_p), ("D", c_void_p), ("g", c_void_p), ("g_stride", c_int), ("third", c_int),
+        ("g_rrdb", c_void_p), ("g_rrdb_stride", c_int), ("wt", c_void_p * 5), ("dw", c_void_p * 5),
+        ("db", c_void_p * 5), ("accumulate", c_int), ("work", c_void_p),
+    ]
+
+
 class WgradDesc(Structure):
     _fields_ = [
         ("dtype", c_int), ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
@@ -223,6 +251,11 @@ _SIGS = {
     "fen_rrdb_conv": (c_int, [POINTER(RrdbConvDesc), c_void_p]),
     "fen_rrdb_block": (c_int, [POINTER(RrdbBlockDesc), c_void_p]),
     "fen_rrdb_first": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
+    "fen_rrdb_dgrad": (c_int, [POINTER(RrdbDgradDesc), c_void_p]),
+    "fen_rrdb_wgrad_work_floats": (c_size_t, [POINTER(RrdbWgradDesc)]),
+    "fen_rrdb_wgrad": (c_int, [POINTER(RrdbWgradDesc), c_void_p]),
+    "fen_rrdb_block_bwd_work_floats": (c_size_t, [c_int] * 4),
+    "fen_rrdb_block_bwd": (c_int, [POINTER(RrdbBlockBwdDesc), c_void_p]),
     "fen_augment_u8": (c_int, [c_int, c_int] + [c_void_p] * 5),
     "fen_bn_work_floats": (c_size_t, [c_int]),
     "fen_bn_stats": (c_int, [c_int, c_size_t, c_int, c_void_p, c_float, c_float] + [c_void_p] * 5),

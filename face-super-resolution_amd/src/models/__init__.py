@@ -5,7 +5,8 @@ ChannelAttention, ResidualGroup, UpsampleModule`, the discriminator (`VGGStyleDi
 `ResidualDenseBlock`, `ESRGANBaseline`, `create_esrgan_baseline`; inference only, esrgan.py) and
 the transfer model (`TransferSRModel`, `TransferModelConfig`, `TrainingStage`, `FaceSpecificHead`,
 `create_transfer_model`, transfer.py: the RRDB backbone + a face-specific head; inference in every
-stage, training in stage 1 -- head only -- until the RRDB backward exists)."""
+stage, training in stage 1 -- head only -- by default and in stages 2 and 3 with
+`train_backbone=True`, the dense blocks' HIP backward)."""
 from .blocks import (RCAB, ChannelAttention, PixelShuffleUpsample, ResidualGroup, UpsampleModule, icnr_init,
                      initialize_weights)
 from .custom import FaceEnhanceNet, FaceEnhanceNetConfig, FaceEnhanceNetLite, create_face_enhance_net

@@ -10,9 +10,12 @@ bit-identical to it -- the upsampler keeps its ICNR init here, nothing re-initia
 
 The forward runs src/hip/transfer.py: GPU tensors only, NCHW fp32 out.  Training: stage 1 (head
 only) trains through autograd -- the backbone runs its inference kernels and saves nothing, the
-head's backward fills every `face_head.*` gradient.  Stages 2 and 3 unfreeze backbone blocks; their
-flags, parameter groups and forward work, but the backward through the dense blocks is not built:
-a backward that reaches a backbone parameter raises NotImplementedError.  fp16 is inference-only.
+head's backward fills every `face_head.*` gradient.  Stages 2 and 3 unfreeze backbone blocks.  A model
+built with `train_backbone=True` trains them: the forward keeps one 192-channel buffer per dense
+block from the first trainable RRDB on (rrdb.trunk(save_from=...)) and the backward runs the dense
+blocks' data and weight gradients (rrdb.trunk_backward).  It is opt-in: without the keyword the
+flags, parameter groups and forward of stages 2 and 3 work as before and a backward that reaches a
+backbone parameter raises NotImplementedError.  fp16 is inference-only.
 
 The kernels are written for the published widths (64 features, 32 growth channels) and power-of-
 two scales; anything else is refused.  Pre-trained weights are read from a local path only.
@@ -80,6 +83,35 @@ class _BackboneTie(torch.autograd.Function):
         raise NotImplementedError(_NO_RRDB_BACKWARD)
 
 
+class _BackboneFn(torch.autograd.Function):
+    """The backbone with RRDBs `first`.. and conv_body trainable (train_backbone=True): x NCHW fp32
+    -> feat [B,64,H,W] (a view of the NHWC buffer); backward fills the gradients of `names`, the
+    backbone parameters that require one, in order."""
+
+    @staticmethod
+    def forward(ctx, x, rt: Runtime, num_block: int, first: int, names, *params):
+        L.check_strip_status()
+        xc = x.detach().contiguous().float()
+        feat, saved = R.trunk(rt.ctx(x.device), rt.wt(x.device), xc, num_block, save_from=first)
+        ctx.rt, ctx.saved, ctx.names = rt, saved, names
+        return as_nchw(feat)
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        _check_grad(ctx.rt)
+        rt, saved = ctx.rt, ctx.saved
+        if saved is None:
+            raise RuntimeError("the backbone's saved buffers were released by an earlier backward")
+        params = dict(rt.module.named_parameters())
+        keys = ["conv_body.weight", "conv_body.bias"]
+        for i in range(saved["first"], saved["num_block"]):
+            keys += [f"body.{i}.rdb{j}.conv{k}.{t}" for j in (1, 2, 3) for k in (1, 2, 3, 4, 5) for t in ("weight", "bias")]
+        G = {k: torch.empty_like(params[k], dtype=torch.float32) for k in keys}
+        R.trunk_backward(rt.ctx(dfeat.device), rt.wt(dfeat.device), G, saved, to_nhwc(dfeat, rt.dtype))
+        ctx.saved = None
+        return (None, None, None, None, None) + tuple(G[k] for k in ctx.names)
+
+
 class _HeadFn(torch.autograd.Function):
     """FaceSpecificHead over its own parameters: feat [B,C,H,W] (channels_last storage is free)
     -> NCHW fp32 [B,3,sH,sW]."""
@@ -141,10 +173,12 @@ class TransferSRModel(nn.Module):
     transfer.py:94-320)."""
 
     def __init__(self, config: Optional[TransferModelConfig] = None, pretrained_path: Optional[str] = None,
-                 precision: str = "fp32"):
+                 precision: str = "fp32", train_backbone: bool = False):
         super().__init__()
         self.config = TransferModelConfig() if config is None else config
         self.precision = precision
+        # opt-in: stages 2 and 3 train through the RRDB backward; off, they refuse (_BackboneTie)
+        self.train_backbone = bool(train_backbone)
         _check_config(self.config.head_channels, self.config.scale_factor)
         self.backbone = self._create_backbone()
         self.face_head = FaceSpecificHead(in_channels=self.config.head_channels, num_blocks=self.config.head_blocks,
@@ -233,6 +267,19 @@ class TransferSRModel(nn.Module):
         feat = T.backbone(rt.ctx(x.device), rt.wt(x.device), xc, self.config.backbone_blocks)
         return as_nchw(feat)              # a view: the head reads the NHWC buffer as it is
 
+    def _run_backbone_saving(self, x: torch.Tensor) -> torch.Tensor:
+        """The training forward of stages 2 and 3 (train_backbone=True): the saved range starts at the
+        first RRDB with a trainable parameter, read from the flags at every forward."""
+        if x.requires_grad:
+            raise NotImplementedError("gradient w.r.t. the LR input image is not provided by the HIP backend")
+        if any(p.requires_grad for p in self.backbone["conv_first"].parameters()):
+            raise NotImplementedError("conv_first is frozen in every training stage (reference transfer.py); its "
+                                      "weight gradient is not built on the HIP backend")
+        named = [(k, p) for k, p in self.backbone.named_parameters() if p.requires_grad]
+        n = self.config.backbone_blocks
+        first = min([int(k.split(".")[1]) for k, _ in named if k.startswith("body.")], default=n)
+        return _BackboneFn.apply(x, self._rt, n, first, tuple(k for k, _ in named), *(p for _, p in named))
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: LR [B,3,H,W] on the GPU, any H, W >= 1 -> SR [B,3,H*scale,W*scale] fp32."""
         _check_input(x, 3)
@@ -242,7 +289,9 @@ class TransferSRModel(nn.Module):
             return T.forward(head.spec, head.ctx(x.device), self._rt.wt(x.device), head.wt(x.device), xc,
                              self.config.backbone_blocks)
         tied = [p for p in self.backbone.parameters() if p.requires_grad]
-        if x.requires_grad or tied:
+        if self.train_backbone and tied:
+            feat = self._run_backbone_saving(x)
+        elif x.requires_grad or tied:
             feat = _BackboneTie.apply(self._run_backbone, x, *tied)
         else:
             feat = self._run_backbone(x)
@@ -284,6 +333,8 @@ class TransferSRModel(nn.Module):
         }
 
 
-def create_transfer_model(pretrained_path: Optional[str] = None, precision: str = "fp32", **kwargs) -> TransferSRModel:
+def create_transfer_model(pretrained_path: Optional[str] = None, precision: str = "fp32", train_backbone: bool = False,
+                          **kwargs) -> TransferSRModel:
     """Factory (reference transfer.py:323-338): kwargs override TransferModelConfig fields."""
-    return TransferSRModel(TransferModelConfig(**kwargs), pretrained_path, precision=precision)
+    return TransferSRModel(TransferModelConfig(**kwargs), pretrained_path, precision=precision,
+                           train_backbone=train_backbone)

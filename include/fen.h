@@ -718,6 +718,100 @@ int fen_rrdb_block(const fen_rrdb_block_desc* d, void* stream);
 int fen_rrdb_first(int dtype, int B, int Ci, int H, int W, const float* x, const float* w, const float* bias,
                    void* y, int y_stride, void* y2, void* stream);
 
+/* ---- the dense blocks' backward (autograd of esrgan.py:85-103 / 69-82; the transfer model's
+ * stages 2 and 3, transfer.py:153-190).  fp32 and bf16 (fp16 is inference-only: FEN_EUNSUPPORTED).
+ * A block's gradients live in a buffer D of the forward buffer's layout, dx | dx1 | .. | dx4 at
+ * pixel stride 192; nothing but the forward buffer itself is needed from the forward: x1..x4 are
+ * stored after LeakyReLU(0.2) and the slope is positive, so its derivative is read off the output,
+ * x_k > 0 ? 1 : 0.2 (torch: pre > 0 ? 1 : 0.2 -- the two differ only where a positive
+ * pre-activation underflows to zero in the storage type).
+ *
+ * fen_rrdb_dgrad: one launch.  v = s * dgrad(dy[..., dy_off : dy_off + Cin); w) for the conv whose
+ * OUTPUT had Cin channels (32 / 64) and whose INPUT had Cout channels (64 + 32 j); w:
+ * fen_pack_conv_w mode 2 of its OIHW weight, [9][Cout][Cin].  accumulate: v += dx[..., 0:Cout);
+ * r1 / r2: v += s1 * r1 + s2 * r2 on channels 0..63; act (the forward buffer): the top 32 channels
+ * written, [Cout - 32, Cout), are multiplied by act > 0 ? 1 : 0.2 at the same pixel and channel;
+ * dx[..., 0:Cout) = v in dtype.  Strides and offsets in elements.  dx may be dy's buffer only when
+ * dy's slice starts at or past Cout (a tile reads its halo of dy and rewrites only its own pixels
+ * of dx, so disjoint channel ranges make the tiles independent), else FEN_EINVAL.  Any H, W >= 1.
+ * FEN_EINVAL: NULL dy / w / dx, non-positive dimensions, a dtype code that is none, pointers not
+ * 16-B aligned, strides / offsets too small or not whole 16-B chunks.  FEN_EUNSUPPORTED: fp16, Cin
+ * not 32 / 64, Cout not 64 + 32 j (j = 0..4), B * H * W >= 2^31.  A refusal launches nothing.   */
+typedef struct {
+    int dtype;
+    int B, H, W;
+    int Cin, Cout;             /* channels of dy read / of dx written                           */
+    const void* dy;            /* NHWC at pixel stride dy_stride, channels from dy_off          */
+    int dy_stride, dy_off;
+    const void* w;             /* mode 2 pack                                                   */
+    void* dx;                  /* NHWC at pixel stride dx_stride >= Cout, channels [0, Cout)    */
+    int dx_stride;
+    int accumulate;
+    float s;
+    const void* r1;            /* NHWC at pixel stride r1_stride, channels 0..63, or NULL       */
+    int r1_stride;
+    float s1;
+    const void* r2;
+    int r2_stride;
+    float s2;
+    const void* act;           /* the forward buffer at pixel stride act_stride, or NULL        */
+    int act_stride;
+} fen_rrdb_dgrad_desc;
+int fen_rrdb_dgrad(const fen_rrdb_dgrad_desc* d, void* stream);
+
+/* fen_rrdb_wgrad: dw[co][ci][kh][kw] (+)= scale * sum_px dy[px][dy_off + co] * x[px + tap][ci],
+ * db[co] (+)= scale * sum_px dy[px][dy_off + co], both operands at a pixel stride: x channels
+ * [0, Cin) of a forward buffer (Cin = 64 + 32 j), dy a 32- or 64-channel slice.  Two launches as
+ * fen_wgrad3x3 (per-block fp32 slabs, then a fixed-order reduction: run-to-run bit-identical).
+ * work: fen_rrdb_wgrad_work_floats() floats (0 for a descriptor that would be refused).  Codes as
+ * fen_rrdb_dgrad; NULL x / dy / dw / work is FEN_EINVAL, db may be NULL.                        */
+typedef struct {
+    int dtype;
+    int B, H, W;
+    int Cin, Cout;
+    const void* x;
+    int x_stride;
+    const void* dy;
+    int dy_stride, dy_off;
+    float scale;
+    float* dw;                 /* OIHW fp32 [Cout][Cin][3][3]                                   */
+    float* db;                 /* [Cout] or NULL                                                */
+    int accumulate;
+    float* work;
+} fen_rrdb_wgrad_desc;
+size_t fen_rrdb_wgrad_work_floats(const fen_rrdb_wgrad_desc* d);
+int fen_rrdb_wgrad(const fen_rrdb_wgrad_desc* d, void* stream);
+
+/* A whole ResidualDenseBlock backwards, mirroring fen_rrdb_block: five fen_rrdb_dgrad launches --
+ * conv5: D[0:192) = 0.2 dgrad5(g), D[0:64) += g, D[160:192) *= lrelu'(x4); conv k = 4..1:
+ * D[0 : 64 + 32 (k - 1)) += dgrad_k(D[64 + 32 (k - 1) : 64 + 32 k)), then its top 32 channels *=
+ * lrelu'(x_{k-1}) for k > 1 -- after which D[0:64) is the gradient of the block's input; then the
+ * weight gradients whose dw entry is not NULL (x = buf, dy = D's slices, and 0.2 g for conv5).
+ * third: the block is an RRDB's third, behind `out * 0.2 + x_rrdb`: g is taken times 0.2.  g_rrdb:
+ * the block is an RRDB's first and D[0:64) += g_rrdb, the gradient of the RRDB's output (both
+ * folded into the launches' epilogues).  g, g_rrdb: channels 0..63 at their pixel strides; neither
+ * is D, and D is not buf (FEN_EINVAL).  work: fen_rrdb_block_bwd_work_floats() floats, needed
+ * when any dw is given.                                                                         */
+typedef struct {
+    int dtype;
+    int B, H, W;
+    int num_feat, num_grow_ch;
+    const void* buf;           /* the forward buffer x | x1 | x2 | x3 | x4                      */
+    void* D;                   /* NHWC [B,H,W,192] of dtype, overwritten                        */
+    const void* g;
+    int g_stride;
+    int third;
+    const void* g_rrdb;        /* or NULL                                                       */
+    int g_rrdb_stride;
+    const void* wt[5];         /* conv1..conv5 packed mode 2                                    */
+    float* dw[5];              /* OIHW fp32, or NULL (then db[k] is NULL too)                   */
+    float* db[5];
+    int accumulate;
+    float* work;
+} fen_rrdb_block_bwd_desc;
+size_t fen_rrdb_block_bwd_work_floats(int dtype, int B, int H, int W);
+int fen_rrdb_block_bwd(const fen_rrdb_block_bwd_desc* d, void* stream);
+
 /* ---- HR batch preparation (src/data/transforms.py:173-279 + to_tensor 260-279) ----
  * src_u8: B uint8 HWC crops [B,P,P,3] (RGB, P even); params: B records {int flip, int
  * jitter, float brightness, contrast, saturation, int rot90_k} drawn by the host; sums: int64
