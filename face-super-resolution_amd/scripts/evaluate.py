@@ -2,7 +2,8 @@
 """Evaluate a checkpoint: per-image PSNR / SSIM over a validation set on the HIP path.
 
     python scripts/evaluate.py --checkpoint X.pth [--data-root DIR | --synthetic N] \\
-        [--batch-size 32] [--precision fp16|bf16|fp32] [--quantize] [--json OUT] [--model custom|esrgan|transfer]
+        [--batch-size 32] [--precision fp16|bf16|fp32] [--quantize] [--json OUT] [--model custom|esrgan|transfer] \\
+        [--lpips-weights FILE]
 
 The checkpoint is loaded weights-only (FaceEnhanceNet.from_pretrained); the images come from
 get_dataloader(mode='val') -- the full images, in order, the last batch partial -- and LR is
@@ -17,6 +18,10 @@ TransferSRModel the same way: --checkpoint is its state dict, plain or under 'mo
 'state_dict', with an optional 'model_config' (the Trainer's checkpoints) or 'config' dict; its
 TransferModelConfig fields are used, other keys ignored.  Prints psnr_mean / psnr_std /
 ssim_mean / ssim_std / num_images; --json OUT writes them with the per-image arrays.
+--lpips-weights FILE (every --model) adds LPIPS v0.1 on the AlexNet backbone through the HIP kernels
+(src.evaluation.LPIPS(weights=FILE): a .pth state dict of AlexNet's convs and the five linear
+layers, never downloaded): lpips_mean / lpips_std and the per-image values, on the same clamped
+(--quantize: 8-bit) SR as PSNR and SSIM, still with one host read at the end.
 """
 import argparse
 import json
@@ -44,6 +49,8 @@ def parse_args(argv=None):
                     help="the compute precision (default: the checkpoint's config, else fp32)")
     ap.add_argument("--quantize", action="store_true", help="quantise SR to 8 bits before measuring")
     ap.add_argument("--json", default=None, metavar="OUT", help="write the results and per-image arrays here")
+    ap.add_argument("--lpips-weights", default=None, metavar="FILE",
+                    help="a .pth state dict of AlexNet + the LPIPS linear layers: also report LPIPS (HIP path)")
     args = ap.parse_args(argv)
     if args.model in ("custom", "transfer") and not args.checkpoint:
         ap.error("the following arguments are required: --checkpoint")
@@ -98,9 +105,11 @@ def eager_metrics(model, args, loader):
     import numpy as np
     import torch
 
-    from src.evaluation.metrics import FLAG_CLAMP, FLAG_QUANTIZE, image_metrics
+    from src.evaluation.metrics import FLAG_CLAMP, FLAG_QUANTIZE, LPIPS, image_metrics, metric_pred
     from src.hip import lib as L
     model = model.to("cuda").eval()
+    lpips = LPIPS(weights=args.lpips_weights) if getattr(args, "lpips_weights", None) else None
+    lps = []
     flags = FLAG_CLAMP | (FLAG_QUANTIZE if args.quantize else 0)
     lib = L.load()
     outs = []
@@ -115,15 +124,27 @@ def eager_metrics(model, args, loader):
                 lr = torch.empty(B, C, H // 4, W // 4, device="cuda")
                 L.check(lib.fen_bicubic_down4(B, C, H, W, hr.data_ptr(), lr.data_ptr(),
                                               torch.cuda.current_stream().cuda_stream), "bicubic_down4")
-            outs.append(image_metrics(model(lr.to("cuda")), hr, 1.0, flags).clone())
+            sr = model(lr.to("cuda"))
+            outs.append(image_metrics(sr, hr, 1.0, flags).clone())
+            if lpips is not None:               # per image, on the SR the other two metrics saw; stays on the device
+                lps.append(lpips.per_image(metric_pred(sr, args.quantize), hr))
     if not outs:
         raise ValueError("evaluate.py: the dataloader yielded no batch")
+    if lps:                                                  # the LPIPS values ride behind each batch's metrics
+        outs = [torch.cat([o.reshape(-1), l]) for o, l in zip(outs, lps)]
     host = [o.cpu().double().numpy() for o in outs]          # the one wait for the stream
+    if lps:
+        lp = np.concatenate([o[-l.numel():] for o, l in zip(host, lps)])
+        host = [o[:-l.numel()].reshape(3, -1) for o, l in zip(host, lps)]
     ps = np.concatenate([o[1] for o in host])
     ss = np.concatenate([o[2] for o in host])
     batch_ssim = np.array([o[2].mean() for o in host])
-    return {"psnr_mean": float(ps.mean()), "psnr_std": float(ps.std()), "ssim_mean": float(batch_ssim.mean()),
-            "ssim_std": float(batch_ssim.std()), "per_image": {"psnr": ps, "ssim": ss}, "num_images": int(ps.size)}
+    res = {"psnr_mean": float(ps.mean()), "psnr_std": float(ps.std()), "ssim_mean": float(batch_ssim.mean()),
+           "ssim_std": float(batch_ssim.std()), "per_image": {"psnr": ps, "ssim": ss}, "num_images": int(ps.size)}
+    if lps:
+        res.update(lpips_mean=float(lp.mean()), lpips_std=float(lp.std()))
+        res["per_image"]["lpips"] = lp
+    return res
 
 
 def main(argv=None) -> int:
@@ -161,7 +182,8 @@ def main(argv=None) -> int:
     # fills its last batch up with images from the start, which would be counted twice)
     loader = get_dataloader(args.data_root, mode="val", batch_size=args.batch_size, num_workers=args.num_workers,
                             hr_patch_size=args.hr_size, synthetic=args.synthetic, device="cpu")
-    res = MetricCalculator(device="cuda").evaluate_dataset(model, loader, quantize=args.quantize)
+    res = MetricCalculator(device="cuda", lpips_weights=args.lpips_weights).evaluate_dataset(
+        model, loader, quantize=args.quantize)
     per = res.pop("per_image")
     res.update(checkpoint=str(args.checkpoint), precision=model.config.precision, quantize=bool(args.quantize))
     print(json.dumps(res))

@@ -13,8 +13,12 @@ cursor and a valid count kept in device memory: nothing comes back to the host i
 loop, the table is copied once at the end, and a partial last batch is padded to the engine's
 batch with the valid count set, so it is weighted by its images.
 
-LPIPS and FID are not built here: as in the reference without the `lpips` / `pytorch_fid`
-packages, `LPIPS().available` is False (forward returns 0) and `compute_fid` returns -1.0.
+`LPIPS(weights=PATH)` is LPIPS v0.1 with the AlexNet backbone on the HIP path (src/hip/lpips.py,
+csrc/lpips.hip): per-image values on the device, the input range decided on the device, no host
+wait; `MetricCalculator(lpips_weights=PATH)` records them next to PSNR / SSIM and reads them with
+the same single copy.  Without `weights` LPIPS is the reference's wrapper of the `lpips` package
+(`available` False and 0 when that is not installed).  FID is not built here: without
+`pytorch_fid`, `compute_fid` returns -1.0.
 """
 from __future__ import annotations
 
@@ -125,12 +129,30 @@ class SSIM(nn.Module):
 
 
 class LPIPS(nn.Module):
-    """Learned Perceptual Image Patch Similarity (metrics.py:81-126): the `lpips` package when
-    it is installed; otherwise `available` is False and forward returns 0, as in the reference."""
+    """Learned Perceptual Image Patch Similarity (metrics.py:81-126).
 
-    def __init__(self, net: str = 'alex', verbose: bool = False):
+    weights=None: the `lpips` package when it is installed; otherwise `available` is False and
+    forward returns 0, as in the reference.  That path decides the input range with a host read
+    of pred.min() per call.
+
+    weights=PATH (a .pth state dict, src.hip.lpips.load_lpips_weights): LPIPS v0.1 on the AlexNet
+    backbone through the HIP kernels, `available` True.  The range rule (pred.min() >= 0: both
+    inputs become 2x - 1) is decided on the device; nothing waits for the host.  AlexNet is the
+    only backbone built."""
+
+    def __init__(self, net: str = 'alex', verbose: bool = False, weights=None):
         super().__init__()
         self.net = net
+        self._hip = None
+        if weights is not None:
+            if net != 'alex':
+                raise NotImplementedError(f"LPIPS(net={net!r}, weights=...): AlexNet (net='alex') is the only "
+                                          "backbone built on the HIP path")
+            from ..hip.lpips import AlexLpips, load_lpips_weights
+            self._hip = AlexLpips(load_lpips_weights(weights))
+            self.loss_fn = None
+            self.available = True
+            return
         try:
             import lpips
             self.loss_fn = lpips.LPIPS(net=net, verbose=verbose)
@@ -140,7 +162,20 @@ class LPIPS(nn.Module):
             self.available = False
             self.loss_fn = None
 
+    def per_image(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """LPIPS per image, [B] on pred's device (zeros when unavailable)."""
+        if self._hip is not None:
+            return self._hip.per_image(pred, target)
+        if not self.available:
+            return torch.zeros(pred.shape[0], device=pred.device)
+        if pred.min() >= 0:             # [0, 1] -> [-1, 1]; a host wait
+            pred = pred * 2 - 1
+            target = target * 2 - 1
+        return self.loss_fn(pred, target).reshape(-1)
+
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self._hip is not None:
+            return self._hip.per_image(pred, target).mean()
         if not self.available:
             return torch.tensor(0.0, device=pred.device)
         if pred.min() >= 0:             # [0, 1] -> [-1, 1]
@@ -149,14 +184,22 @@ class LPIPS(nn.Module):
         return self.loss_fn(pred, target).mean()
 
 
+def metric_pred(sr: torch.Tensor, quantize: bool = False) -> torch.Tensor:
+    """SR as fen_image_metrics sees it under FLAG_CLAMP (| FLAG_QUANTIZE): clamped to [0, 1], then
+    floor(x * 255) / 255 in fp32 -- the tensor LPIPS is computed on, so all three metrics measure
+    the same image."""
+    sr = sr.float().clamp(0, 1)
+    return torch.floor(sr * 255) / 255 if quantize else sr
+
+
 class MetricCalculator:
     """Metric calculator for evaluation (metrics.py:129-224)."""
 
-    def __init__(self, device: str = 'cuda'):
+    def __init__(self, device: str = 'cuda', lpips_weights=None):
         self.device = torch.device(device if torch.cuda.is_available() else 'cpu')
         self.psnr = PSNR().to(self.device)
         self.ssim = SSIM().to(self.device)
-        self.lpips = LPIPS().to(self.device)
+        self.lpips = LPIPS(weights=lpips_weights).to(self.device)
         self._engines: Dict[tuple, tuple] = {}
 
     @torch.no_grad()
@@ -205,7 +248,13 @@ class MetricCalculator:
         synchronisation until the single copy of the table after the last batch.  Returns the
         reference's psnr_mean / psnr_std (over images) and ssim_mean / ssim_std (over per-batch
         means, a batch mean covering its valid images), float64 on the host, plus per_image =
-        {'psnr', 'ssim'} arrays and num_images."""
+        {'psnr', 'ssim'} arrays and num_images.
+
+        With LPIPS available: lpips_mean / lpips_std over images and per_image['lpips'], computed
+        on the same clamped (quantize: 8-bit) SR.  On the HIP path (lpips_weights) the per-image
+        values go into the same device buffer as the PSNR / SSIM table and come back with that
+        one copy: no extra host wait.  The `lpips`-package path still waits once per batch (its
+        range test reads pred.min() on the host)."""
         if self.device.type != 'cuda':
             raise RuntimeError("evaluate_dataset runs the HIP inference engine: it needs a ROCm GPU")
         try:
@@ -217,9 +266,9 @@ class MetricCalculator:
         model.eval()
         lib = L.load()
         flags = FLAG_CLAMP | (FLAG_QUANTIZE if quantize else 0)
-        eng = hr_buf = state = table = out = work = None
+        eng = hr_buf = state = table = lp_table = out = work = None
         counts: List[int] = []
-        lpips_vals = []
+        seen = 0
         for batch in batches:
             hr = batch['hr']
             lr = batch.get('lr')
@@ -230,9 +279,10 @@ class MetricCalculator:
                 cap = len(dataloader) * B
                 hr_buf = torch.zeros(B, C, H, W, device=self.device)
                 # one buffer, one copy at the end: int32 [cursor, nvalid], then the table's
-                # 2 x cap floats
-                state = torch.zeros(2 + 2 * cap, dtype=torch.int32, device=self.device)
-                table = state[2:].view(torch.float32).view(2, cap)
+                # 2 x cap floats, then cap floats of per-image LPIPS
+                state = torch.zeros(2 + 3 * cap, dtype=torch.int32, device=self.device)
+                table = state[2:2 + 2 * cap].view(torch.float32).view(2, cap)
+                lp_table = state[2 + 2 * cap:].view(torch.float32)
                 out = torch.empty(3, B, device=self.device)
                 work = torch.empty(max(int(lib.fen_image_metrics_work_floats(B, C, H, W)), 1), device=self.device)
                 state[1] = B
@@ -254,8 +304,10 @@ class MetricCalculator:
             eng.replay()
             image_metrics(eng.out, hr_buf, 1.0, flags, table=table, cursor=state[0:1], nvalid=state[1:2], out=out,
                           work=work)
-            if self.lpips.available:
-                lpips_vals.append(self.lpips(eng.out[:n].clamp(0, 1), hr_buf[:n]).reshape(1))
+            if self.lpips.available and seen + n <= cap:
+                # the host knows every batch's size, so the offset needs no device cursor
+                lp_table[seen:seen + n].copy_(self.lpips.per_image(metric_pred(eng.out, quantize), hr_buf)[:n])
+            seen += n
             counts.append(n)
         if eng is None:
             raise ValueError("evaluate_dataset: the dataloader yielded no batch")
@@ -265,7 +317,7 @@ class MetricCalculator:
         if total > cap:
             raise RuntimeError(f"evaluate_dataset: {total} images for a table of {cap} (len(dataloader) x the first "
                                "batch's size): the per-image record overflowed")
-        tab = host[2:].view(torch.float32).view(2, cap).numpy().astype(np.float64)
+        tab = host[2:2 + 2 * cap].view(torch.float32).view(2, cap).numpy().astype(np.float64)
         ps, ss = tab[0, :total], tab[1, :total]
         ends = np.cumsum(counts)
         batch_ssim = np.array([ss[e - c:e].mean() for c, e in zip(counts, ends)])
@@ -274,10 +326,11 @@ class MetricCalculator:
             'ssim_mean': float(np.mean(batch_ssim)), 'ssim_std': float(np.std(batch_ssim)),
             'per_image': {'psnr': ps, 'ssim': ss}, 'num_images': total,
         }
-        if lpips_vals:
-            lp = torch.cat(lpips_vals).double().cpu().numpy()
+        if self.lpips.available:
+            lp = host[2 + 2 * cap:].view(torch.float32).numpy().astype(np.float64)[:total]
             results['lpips_mean'] = float(np.mean(lp))
             results['lpips_std'] = float(np.std(lp))
+            results['per_image']['lpips'] = lp
         return results
 
 
@@ -302,4 +355,4 @@ def compute_fid(real_images: List[np.ndarray], fake_images: List[np.ndarray], de
 
 
 __all__ = ["psnr", "psnr_batch", "PSNR", "SSIM", "LPIPS", "MetricCalculator", "compute_fid", "image_metrics",
-           "FLAG_CLAMP", "FLAG_QUANTIZE"]
+           "metric_pred", "FLAG_CLAMP", "FLAG_QUANTIZE"]

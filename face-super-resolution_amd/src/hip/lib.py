@@ -248,6 +248,13 @@ _SIGS = {
     "fen_image_metrics": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int, c_float, c_float, c_float, c_int, c_void_p,
                                                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                                                  c_void_p]),
+    "fen_conv2d_f32_pack": (c_int, [c_int] * 5 + [c_void_p] * 3),
+    "fen_conv2d_f32": (c_int, [c_int] * 9 + [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
+    "fen_maxpool3s2_f32": (c_int, [c_int] * 4 + [c_void_p] * 3),
+    "fen_lpips_work_floats": (c_size_t, [c_int] * 3),
+    "fen_lpips_prep": (c_int, [c_int] * 3 + [c_void_p] * 3 + [c_size_t, c_void_p, c_void_p]),
+    "fen_lpips_head": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "fen_lpips_finish": (c_int, [c_int] * 3 + [c_void_p, c_size_t, c_void_p, c_void_p]),
     "fen_rrdb_conv": (c_int, [POINTER(RrdbConvDesc), c_void_p]),
     "fen_rrdb_block": (c_int, [POINTER(RrdbBlockDesc), c_void_p]),
     "fen_rrdb_first": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),

@@ -657,6 +657,52 @@ int fen_image_metrics(int B, int C, int H, int W, const float* pred, const float
                       float* work, float* out, float* table, int table_cap, int* cursor, const int* nvalid,
                       void* stream);
 
+/* ---- LPIPS v0.1, AlexNet backbone (src/evaluation/metrics.py:81-126: lpips.LPIPS(net='alex')),
+ * forward only, fp32, one value per image (csrc/lpips.hip) ----
+ * Every call launches on `stream`, synchronises nothing, uses no atomics (two runs are
+ * bit-identical) and validates its arguments before any launch.  x / wp / y of fen_conv2d_f32,
+ * x / y of fen_maxpool3s2_f32 and x0 of fen_lpips_prep are 16-B aligned (else FEN_EINVAL); the
+ * other pointers need only their element's alignment.
+ *
+ * fen_conv2d_f32: y[N,Ho,Wo,Cout] = (relu ? max(0, .) : .)(conv(x[N,H,W,Cin], filter) + bias),
+ * Ho = (H + 2 pad - KH) / stride + 1 (floor), zero padding, NHWC fp32 in and out, bias [Cout] or
+ * NULL.  An implicit GEMM on the exact-fp32 MFMA with fp32 accumulation: every output element is
+ * a fixed-order blocked sum (fmaf chains of 16 k, added in groups of 4, 8 and the rest), k =
+ * (kh, kw, ci) in that order.  wp is the filter packed to [KH KW Cin][Cout]
+ * by fen_conv2d_f32_pack from torch's [Cout][Cin_src][KH][KW] (Cin_pad >= Cin_src input channels
+ * per position, the added ones zero: AlexNet's first conv runs with Cin 3 -> 4).
+ * FEN_EINVAL: a NULL or misaligned x / wp / y, a non-positive size, pad < 0.  FEN_EUNSUPPORTED:
+ * Cout not a multiple of 64, Cin not a multiple of 4 (so K = KH KW Cin is a multiple of 4), an
+ * empty output (H + 2 pad < KH or W + 2 pad < KW), more than 2^30 output or input pixels.
+ *
+ * fen_maxpool3s2_f32: y[N,(H-3)/2+1,(W-3)/2+1,C] = max over 3x3 windows at stride 2, no padding
+ * (torch max_pool2d(3, 2), bit-equal).  FEN_EUNSUPPORTED: C not a multiple of 4, H or W < 3.
+ *
+ * The LPIPS sequence for pred / target [B,3,H,W] (NCHW fp32), H, W >= 31 (the smallest input for
+ * which every feature map is non-empty), with work = fen_lpips_work_floats(B, H, W) floats that
+ * the caller owns and passes to all three (0 for a shape that is refused: B < 1, H or W < 31,
+ * 2 B H W > 2^28; a shorter work_floats is FEN_EINVAL, a refused shape FEN_EUNSUPPORTED):
+ *   fen_lpips_prep    x0[2B,H,W,4]: images 0..B-1 from pred, B..2B-1 from target, each value
+ *                     ((f ? 2 v - 1 : v) - shift[c]) / scale[c], channel 3 zero; f = (min over
+ *                     pred >= 0) is decided on the device (a min reduction leaves a flag in work)
+ *                     and holds for both tensors
+ *   AlexNet features  conv 11/4/2 3(4)->64, pool, conv 5/1/2 64->192, pool, conv 3/1/1 192->384,
+ *                     384->256, 256->256, every conv with ReLU: fen_conv2d_f32 / fen_maxpool3s2_f32
+ *   fen_lpips_head    tap = 0..4, feat = that conv's output [2B,h,w,C] (C = 64, 192, 384, 256,
+ *                     256), lin[C]: per pixel sum_c lin[c] (a_c / (|a| + 1e-10) - b_c / (|b| +
+ *                     1e-10))^2 between image b and image B + b, per-image partial sums into work
+ *   fen_lpips_finish  out[b] = sum over the taps of the tap's mean over its pixels, tap order    */
+int fen_conv2d_f32_pack(int Cout, int Cin_src, int KH, int KW, int Cin_pad, const float* w, float* wp, void* stream);
+int fen_conv2d_f32(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, const float* x,
+                   const float* wp, const float* bias, int relu, float* y, void* stream);
+int fen_maxpool3s2_f32(int N, int H, int W, int C, const float* x, float* y, void* stream);
+size_t fen_lpips_work_floats(int B, int H, int W);
+int fen_lpips_prep(int B, int H, int W, const float* pred, const float* target, float* work, size_t work_floats,
+                   float* x0, void* stream);
+int fen_lpips_head(int B, int H, int W, int tap, const float* feat, const float* lin, float* work,
+                   size_t work_floats, void* stream);
+int fen_lpips_finish(int B, int H, int W, const float* work, size_t work_floats, float* out, void* stream);
+
 /* ---- ESRGAN baseline, RRDBNet (src/models/esrgan.py:17-103), inference only ----
  * 3x3 / pad 1 convs over a growing channel concatenation (csrc/rrdb.hip).  A ResidualDenseBlock
  * (esrgan.py:85-103) lives in one NHWC buffer of 192 channels per pixel, x | x1 | x2 | x3 | x4
